@@ -2,6 +2,13 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg4|cfg5|cfg2]
                     [--generator planted|uniform] [--mode eval|predict]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line of the metric (value,
+ms_per_step, stage_ms, records, library).  `--full` adds everything else described below:
+the CifHr rooflines, the predict / uniform / multi-scale / cfg2 / cfg5 lines and the CPU
+baselines (each with its own --no-* switch).  `--dump-outputs DIR` writes the records of the
+last timed step as DIR/<name>.npy (dump_outputs).
 
 One step = one full decode (CifHr -> seeds -> CafScored -> seed loop / grow ->
 force-complete -> NMS) of the rank's resident batch of synthetic fields, plus the packing
@@ -14,7 +21,8 @@ pack into device memory and send from there).  Inputs are generated once and sta
 `--gpus N` without a torchrun environment starts the N rank processes itself (before any
 GPU call in this process) and exits with their status.
 
-Rank 0 prints ONE JSON line.  `roofline` is the CifHr accumulation of the metric: the
+Rank 0 prints ONE JSON line.  The objects described from here on are measured with --full
+only.  `roofline` is the CifHr accumulation of the metric: the
 dense CifHr.accumulated map (pp_cifhr) of the same resident batch, timed with HIP events
 on the launch stream; algorithmic bytes = 4*K*(5*H*W + H'*W') per image
 over its launch time.  `roofline_decoder_cifhr` is the decoder's own block-sparse CifHr
@@ -58,6 +66,11 @@ def parse():
     p.add_argument('--generator', default='planted', choices=('planted', 'uniform'))
     p.add_argument('--mode', default='eval', choices=('eval', 'predict'))
     p.add_argument('--batch', type=int, default=None, help='images per GPU (override)')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what the metric does not need: the CifHr rooflines, the '
+                        'predict / uniform / multi-scale / cfg2 / cfg5 lines, the CPU baselines')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the records of the last timed step as DIR/<name>.npy')
     p.add_argument('--cpu-seconds', type=float, default=18.0,
                    help='budget of the oracle CPU baseline sample (rank 0, N=1)')
     p.add_argument('--no-cpu-baseline', action='store_true')
@@ -77,7 +90,10 @@ def parse():
     p.add_argument('--no-overlap', action='store_true',
                    help='run each step on one stream (no front / back half overlap of '
                         'consecutive steps, engine.DecodePipeline)')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.dump_outputs and WORKLOADS[args.workload or 'cfg3'].get('stages', 15) != 15:
+        p.error('--dump-outputs needs a workload that decodes records (not cfg2)')
+    return args
 
 
 def spawn_ranks(n):
@@ -205,6 +221,7 @@ def main():
     counters = {'refetch_steps': 0, 'pack_bytes': 0}
     gather = {'steps': 0, 'verified_steps': 0, 'ranks_seen': world, 'full_record_steps': 0,
               'bytes': 0}
+    last_out = {}  # (records, offsets) of the newest finished step (rank 0: of all ranks)
 
     def timed_run(cif, caf, steps, warmup, heads=None, skel=None, n_stages=None, run_cfg=None):
         """warmup + `steps` timed decode steps of one resident batch (cif / caf, or a
@@ -256,7 +273,8 @@ def main():
             if pending is None:
                 torch.cuda.synchronize()
             elif world == 1 or local:
-                recs, _ = pending.result()
+                recs, offs = pending.result()
+                last_out['records'] = (recs, offs)
                 counters['refetch_steps'] += int(recs.dtype == ANN_DTYPE)
                 counters['pack_bytes'] = len(recs) * recs.dtype.itemsize
                 n_recs = len(recs)
@@ -278,9 +296,10 @@ def main():
                 if comm_dev.type == 'cpu':
                     src = src[:int(counts.sum()) * width].cpu()
                 rep = {}
-                recs, _ = gather_packed(src, counts, dist, n_max=n_img, dtype=pending.dtype,
-                                        device=comm_dev, stream=comm, full=full, k=k_img,
-                                        c=len(skel), report=rep)
+                recs, offs = gather_packed(src, counts, dist, n_max=n_img, dtype=pending.dtype,
+                                           device=comm_dev, stream=comm, full=full, k=k_img,
+                                           c=len(skel), report=rep)
+                last_out['records'] = (recs, offs)
                 n_recs = len(recs) if recs is not None else 0
                 if timed:
                     rank_ms['gather'] += 1e3 * (time.perf_counter() - t_gather)
@@ -361,26 +380,13 @@ def main():
     log('rank {}/{}: {} on {}'.format(rank, world, args.workload, dev))
     elapsed, stage_avg, n_anns = timed_run(cif, caf, args.steps, args.warmup)
     log('main workload done')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out['records'])
+        log('outputs written to {}'.format(args.dump_outputs))
 
     images = batch * world * args.steps
     value = images / elapsed
     ms_step = 1e3 * elapsed / args.steps
-    hh, ww = (h - 1) * 8 + 1, (w - 1) * 8 + 1
-    cifhr_bytes, hr_tiles, sector_bytes = cifhr_stage_bytes(cif_h, 8, cfg.cif_threshold,
-                                                            cfg.seed_threshold)
-    achieved = cifhr_bytes / (stage_avg[0] * 1e-3) / 1e9
-    if world > 1 and args.backend == 'gloo':
-        # the rehearsal's ranks share one GPU: 8 ranks x two 14.3 GB workspaces fill most of
-        # its 288 GB, so the decode workspaces go before the dense map's 9.6 GB per rank
-        # (memory budget)
-        import gc
-        pipe, eng = None, None
-        gc.collect()
-        torch.cuda.empty_cache()
-        dist.barrier()
-    dense_ms = dense_cifhr_ms(cif, cfg, stream, args.steps, args.warmup)
-    dense_bytes = 4 * k * (5 * h * w + hh * ww) * batch  # SURVEY.md §8d, per launch
-    dense_gbs = dense_bytes / (dense_ms * 1e-3) / 1e9
     line = {
         'metric': 'decoder images/sec + ms/image, 17-CIF/19-CAF @80x80; CifHr HBM GB/s vs '
                   'roofline',
@@ -415,29 +421,6 @@ def main():
         'stage_ms': {n: round(float(v), 4) for n, v in zip(names, stage_avg)},
         'annotations_per_image': round(n_anns / max(1, args.steps * batch * world), 3)
         if stages & STAGE_GROW else None,
-        # CifHr accumulation (the metric's "CifHr HBM GB/s"): CifHr.accumulated of the
-        # reference API, the dense (K, H', W') map, pp_cifhr = cifhr_list_kernel +
-        # cifhr_tile_kernel, timed on its own over `steps` launches on the same batch
-        'roofline': {
-            'bound': 'hbm', 'kernel': 'cifhr_list_kernel + cifhr_tile_kernel (pp_cifhr)',
-            'achieved': round(dense_gbs, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-            'frac': round(dense_gbs / PEAK_HBM_GBS, 4), 'traffic': None,
-            'algorithmic_bytes_per_launch': dense_bytes, 'ms_per_launch': round(dense_ms, 4),
-        },
-        # the decoder's own CifHr (inside `value`): the block-sparse map, written only where
-        # splat boxes land; latency-bound per field, far below the dense byte count
-        'roofline_decoder_cifhr': {
-            'bound': 'hbm', 'kernel': 'cifhr_fused_kernel (CifHr + seed emission)',
-            'achieved': round(achieved, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-            'frac': round(achieved / PEAK_HBM_GBS, 4),
-            'algorithmic_bytes_per_launch': cifhr_bytes, 'traffic': None,
-            # the same bytes counted in the 64-B lines they live in: the x / y / scale rows
-            # of kept cells are 4-B gathers, a line per run of kept cells
-            'line_granular_bytes_per_launch': sector_bytes,
-            'written_block_frac': round(hr_tiles, 6),
-            'us_per_image': round(1e3 * stage_avg[0] / batch, 4),
-            'dense_equivalent_gbs': round(dense_bytes / (stage_avg[0] * 1e-3) / 1e9, 1),
-        },
     }
     if world > 1:
         # the multi-GPU hand-over proves itself: every gathered step (the untimed one before
@@ -452,8 +435,50 @@ def main():
         # a step; overlapped steps share the device), host ms per step blocked on the
         # step's records, host ms per step in the gather (rank 0: receiving and checking)
         line['per_rank'] = per_rank
-    default_run = (args.workload in ('cfg3', 'cfg4') and args.generator == 'planted' and
-                   args.mode == 'eval' and batch == WORKLOADS['cfg3']['batch'])
+    # everything below is measured only with --full
+    default_run = (args.full and args.workload in ('cfg3', 'cfg4') and
+                   args.generator == 'planted' and args.mode == 'eval' and
+                   batch == WORKLOADS['cfg3']['batch'])
+    if args.full:
+        hh, ww = (h - 1) * 8 + 1, (w - 1) * 8 + 1
+        cifhr_bytes, hr_tiles, sector_bytes = cifhr_stage_bytes(cif_h, 8, cfg.cif_threshold,
+                                                                cfg.seed_threshold)
+        achieved = cifhr_bytes / (stage_avg[0] * 1e-3) / 1e9
+        if world > 1 and args.backend == 'gloo':
+            # the rehearsal's ranks share one GPU: 8 ranks x two 14.3 GB workspaces fill most
+            # of its 288 GB, so the decode workspaces go before the dense map's 9.6 GB per
+            # rank (memory budget)
+            import gc
+            pipe, eng = None, None
+            gc.collect()
+            torch.cuda.empty_cache()
+            dist.barrier()
+        dense_ms = dense_cifhr_ms(cif, cfg, stream, args.steps, args.warmup)
+        dense_bytes = 4 * k * (5 * h * w + hh * ww) * batch  # SURVEY.md §8d, per launch
+        dense_gbs = dense_bytes / (dense_ms * 1e-3) / 1e9
+        # CifHr accumulation (the metric's "CifHr HBM GB/s"): CifHr.accumulated of the
+        # reference API, the dense (K, H', W') map, pp_cifhr = cifhr_list_kernel +
+        # cifhr_tile_kernel, timed on its own over `steps` launches on the same batch
+        line['roofline'] = {
+            'bound': 'hbm', 'kernel': 'cifhr_list_kernel + cifhr_tile_kernel (pp_cifhr)',
+            'achieved': round(dense_gbs, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+            'frac': round(dense_gbs / PEAK_HBM_GBS, 4), 'traffic': None,
+            'algorithmic_bytes_per_launch': dense_bytes, 'ms_per_launch': round(dense_ms, 4),
+        }
+        # the decoder's own CifHr (inside `value`): the block-sparse map, written only where
+        # splat boxes land; latency-bound per field, far below the dense byte count
+        line['roofline_decoder_cifhr'] = {
+            'bound': 'hbm', 'kernel': 'cifhr_fused_kernel (CifHr + seed emission)',
+            'achieved': round(achieved, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / PEAK_HBM_GBS, 4),
+            'algorithmic_bytes_per_launch': cifhr_bytes, 'traffic': None,
+            # the same bytes counted in the 64-B lines they live in: the x / y / scale rows
+            # of kept cells are 4-B gathers, a line per run of kept cells
+            'line_granular_bytes_per_launch': sector_bytes,
+            'written_block_frac': round(hr_tiles, 6),
+            'us_per_image': round(1e3 * stage_avg[0] / batch, 4),
+            'dense_equivalent_gbs': round(dense_bytes / (stage_avg[0] * 1e-3) / 1e9, 1),
+        }
     if default_run:
         tr = committed_traffic()
         for key in ('roofline', 'roofline_decoder_cifhr'):
@@ -552,7 +577,7 @@ def main():
             }
             del c5, a5
             log('cfg5 {} done'.format(g))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         uc = synthetic.batch('uniform', 64, h, w, n_caf=len(skeleton)) if default_run else None
         line['cpu_baseline'] = cpu_baseline(cif_h, caf_h, skeleton, cfg, args.cpu_seconds,
                                             *(uc or (None, None)))
@@ -561,6 +586,56 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs, all files together
+
+
+def dump_outputs(path, recs, offsets, limit=DUMP_LIMIT):
+    """Write one step's records (what PendingRecords.result() / gather_packed hand to the
+    caller: compact pp_pack_compact records or full pp_ann ones, and the per-image offsets)
+    as path/<field>.npy, one float array per record field in the full record's layout, the
+    keypoint axis cut to the records' K: data, joint_scales, decoding_xyv (float32); score,
+    image, n_decoding, n_frontier, offsets (float64); decoding_pairs, frontier_pairs
+    (float32).  Slots past n_decoding / n_frontier are written as zeros (they carry no
+    result).  When the arrays would pass `limit` bytes, a fixed seeded sample of the records
+    is written and rows.npy (float64) names the sampled records; offsets.npy always covers
+    every image."""
+    from openpifpaf_amd._abi import ANN_DTYPE
+    from openpifpaf_amd.distributed import expand_compact
+    os.makedirs(path, exist_ok=True)
+    offsets = np.asarray(offsets, dtype=np.float64)
+    k = recs.dtype['data'].shape[0] if recs.dtype != ANN_DTYPE else None
+    if recs.dtype != ANN_DTYPE:
+        recs = expand_compact(recs)
+    if k is None:
+        k = int(recs['n_keypoints'].max(initial=1))
+    n_f = recs.dtype['frontier_pairs'].shape[0]
+    row_bytes = 4 * (3 * k + k + 6 * k + 2 * k + 2 * n_f) + 8 * 4
+    budget = (limit - offsets.nbytes - 4096) // (row_bytes + 8)
+    rows = None
+    if len(recs) > budget:
+        rows = np.sort(np.random.default_rng(0).choice(len(recs), int(budget), replace=False))
+        recs = recs[rows]
+    live_d = (np.arange(k)[None, :] < recs['n_decoding'][:, None])[:, :, None]
+    live_f = (np.arange(n_f)[None, :] < recs['n_frontier'][:, None])[:, :, None]
+    out = {
+        'offsets': offsets,
+        'data': recs['data'][:, :k].astype(np.float32),
+        'joint_scales': recs['joint_scales'][:, :k].astype(np.float32),
+        'score': recs['score'].astype(np.float64),
+        'image': recs['image'].astype(np.float64),
+        'n_decoding': recs['n_decoding'].astype(np.float64),
+        'n_frontier': recs['n_frontier'].astype(np.float64),
+        'decoding_pairs': np.where(live_d, recs['decoding_pairs'][:, :k], 0).astype(np.float32),
+        'decoding_xyv': np.where(live_d, recs['decoding_xyv'][:, :k], 0).astype(np.float32),
+        'frontier_pairs': np.where(live_f, recs['frontier_pairs'], 0).astype(np.float32),
+    }
+    if rows is not None:
+        out['rows'] = rows.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) + 128 * len(out) <= limit
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
 
 
 def library_identity():

@@ -12,7 +12,7 @@ for rep in 1 2; do
     lv="$v"; ev="PP_AB_NONE=1"
     [ "$v" = "-" ] && lv=""
     case "$v" in *=*) ev="${v//,/ }"; lv="";; esac
-    env $ev PP_LIB_VARIANT=$lv timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-multi \
+    env $ev PP_LIB_VARIANT=$lv timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-multi \
       > gpurun_out/ab_${TAG}_${v}_${rep}.json 2> gpurun_out/ab_${TAG}_${v}_${rep}.err || exit $?
     python3 - gpurun_out/ab_${TAG}_${v}_${rep}.json "$v" <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for G in planted uniform; do
   timeout -k 10 180 rocprofv3 --kernel-trace --stats -d "$OUT/$G" -o run --output-format csv \
-    -- python3 "$R/bench.py" --workload cfg2 --generator $G --steps 50 --warmup 5 \
+    -- python3 "$R/bench.py" --full --workload cfg2 --generator $G --steps 50 --warmup 5 \
     --no-cpu-baseline > "$OUT/${G}_bench.json" 2> "$OUT/${G}.err" || exit $?
   python3 -c "
 import csv

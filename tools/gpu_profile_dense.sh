@@ -10,7 +10,7 @@ R="$GRAFT_REPO_ROOT"
 OUT="$R/gpurun_out/profd_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-uniform --no-multi --no-configs"
+COMMON="--full --no-cpu-baseline --no-uniform --no-multi --no-configs"
 run() {  # name, bench args
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o run --output-format csv \

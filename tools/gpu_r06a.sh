@@ -3,16 +3,16 @@
 set -u
 TAG=${1:-r06a}
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+LOGS=$(realpath -m "${LOGS:-bench_out}"); mkdir -p "$LOGS"  # LOGS=<dir>: where the outputs go
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu -p no:cacheprovider \
-  --timeout 120 --timeout-method thread > gpurun_out/${TAG}_tests.log 2>&1
+  --timeout 120 --timeout-method thread > $LOGS/${TAG}_tests.log 2>&1
 rc=$?
-tail -3 gpurun_out/${TAG}_tests.log
+tail -3 $LOGS/${TAG}_tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --gpus 8 --backend gloo --workload cfg4 --no-uniform \
-  --no-multi --no-configs --no-cpu-baseline > gpurun_out/${TAG}_bench_gloo8.json \
-  2> gpurun_out/${TAG}_bench_gloo8.err || exit $?
-cat gpurun_out/${TAG}_bench_gloo8.json
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > gpurun_out/${TAG}_bench.json \
-  2> gpurun_out/${TAG}_bench.err || exit $?
-cat gpurun_out/${TAG}_bench.json
+timeout -k 10 600 python -u bench.py --full --gpus 8 --backend gloo --workload cfg4 --no-uniform \
+  --no-multi --no-configs --no-cpu-baseline > $LOGS/${TAG}_bench_gloo8.json \
+  2> $LOGS/${TAG}_bench_gloo8.err || exit $?
+cat $LOGS/${TAG}_bench_gloo8.json
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $LOGS/${TAG}_bench.json \
+  2> $LOGS/${TAG}_bench.err || exit $?
+cat $LOGS/${TAG}_bench.json

@@ -5,15 +5,15 @@
 set -u
 TAG=${1:-r01c}
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+LOGS=$(realpath -m "${LOGS:-bench_out}"); mkdir -p "$LOGS"  # LOGS=<dir>: where the outputs go
 timeout -k 10 540 python -u -m pytest tests -x -q -m gpu -p no:cacheprovider \
-  --timeout 120 --timeout-method thread > gpurun_out/${TAG}_tests.log 2>&1
+  --timeout 120 --timeout-method thread > $LOGS/${TAG}_tests.log 2>&1
 rc=$?
-tail -3 gpurun_out/${TAG}_tests.log
+tail -3 $LOGS/${TAG}_tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || exit $?
-tail -1 gpurun_out/${TAG}_smoke.log
-timeout -k 10 300 python -u bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit $?
-cat gpurun_out/${TAG}_bench.json
+timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $LOGS/${TAG}_smoke.log 2>&1 || exit $?
+tail -1 $LOGS/${TAG}_smoke.log
+timeout -k 10 300 python -u bench.py --full > $LOGS/${TAG}_bench.json 2> $LOGS/${TAG}_bench.err || exit $?
+cat $LOGS/${TAG}_bench.json
 [ "${PROFILE:-1}" = "1" ] && bash tools/gpu_profile.sh "$TAG"
 true
