@@ -432,6 +432,40 @@ int pp_fields_from_conv(const float *d_conv, int32_t n_img, int32_t n_fields, in
                         int32_t h, int32_t w, int32_t quad, float *d_out, void *stream);
 
 /*
+ * pp_fields_from_conv with the conv output's type, the un-flip of a horizontally mirrored
+ * pass and a field range of the output, still one read of the conv output.  With
+ * conv_dtype PP_DTYPE_F32, mirror 0, no tables, out_fields = n_fields and out_field0 = 0 it
+ * is pp_fields_from_conv (which calls it that way).
+ *   conv_dtype  PP_DTYPE_F32 / F16 / BF16: the element type of d_conv.  A half value is
+ *               converted exactly to float32 first, so the result equals the float32
+ *               ingest of the up-converted tensor.  (Under autocast the reference would
+ *               round its sigmoid / exp to half; the fields written here are float32 and
+ *               are not rounded to half.)
+ *   mirror      1: output column X reads source column W-1-X, and the x component of every
+ *               vector the index grid is added to is negated before X is added (CIF: its
+ *               vector; CAF: both; CifDet: the first vector only, not (w, h))
+ *   src_field   host (n_fields) or NULL: output field f reads conv field src_field[f]
+ *               (PifHFlip / PafHFlip's flip_indices, heads.py:149-152, 184-190)
+ *   swap_ends   host (n_fields) or NULL, CAF only: 1 = output (x1, y1) takes conv vector
+ *               2 and (x2, y2) conv vector 1 (PafHFlip's reverse_direction).  Regressions
+ *               only: confidence, logb1 / logb2 and scale1 / scale2 stay in place, as the
+ *               reference exchanges only the regressions (heads.py:209-212).
+ *   d_out       (n_img, out_fields, 5 | 9 | 7, H, W); fields out_field0 .. out_field0 +
+ *               n_fields - 1 of every image are written, the others are left alone
+ * src_field and swap_ends are copied into the kernel arguments (at most 64 fields); they
+ * need not outlive the call.  Checked before any launch: unknown dtype or layout,
+ * src_field[i] outside [0, n_fields), swap_ends with a non-CAF layout -> PP_EINVAL; tables
+ * with n_fields > 64, out_field0 < 0 or out_field0 + n_fields > out_fields -> PP_ESHAPE.
+ */
+#define PP_DTYPE_F32 0
+#define PP_DTYPE_F16 1
+#define PP_DTYPE_BF16 2
+int pp_fields_from_conv_ex(const void *d_conv, int32_t conv_dtype, int32_t n_img,
+                           int32_t n_fields, int32_t layout, int32_t h, int32_t w, int32_t quad,
+                           int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
+                           float *d_out, int32_t out_fields, int32_t out_field0, void *stream);
+
+/*
  * nms.Keypoints.annotations (nms.py:17-57) over caller records, n_img independent groups:
  * d_anns (n_img, ann_capacity) with d_counts[i] records in group i (modified in place as
  * the reference modifies its Annotation objects: joints below keypoint_threshold zeroed,
