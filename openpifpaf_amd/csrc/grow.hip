@@ -24,220 +24,9 @@
 // NMS (nms.py:17-57) is one 8-wave workgroup per image.  Float arithmetic is f32
 // op-for-op as NumPy evaluates it (NEP 50); np.exp is computed correctly rounded through
 // f64.
-#include "pp_common.hpp"
-
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <mutex>
-
-// Diagnostic build only (-DPP_STAMPS, libpifpaf_amd_stamps.so): per-section shader-cycle
-// sums of the decode kernel, dumped to $PP_STAMPS_OUT.  The product build compiles these
-// to nothing.
-#ifdef PP_STAMPS
-#define STAMP_DECL                                                                          \
-    uint64_t st_acc[kStampSlots] = {};                                                     \
-    uint64_t st_t = __builtin_amdgcn_s_memtime();
-#define STAMP(i)                                                                            \
-    do {                                                                                    \
-        const uint64_t t_ = __builtin_amdgcn_s_memtime();                                   \
-        st_acc[i] += t_ - st_t;                                                             \
-        st_t = t_;                                                                          \
-    } while (0)
-#define STAMP_FLUSH(ph)                                                                     \
-    if (lane == 0 && g.stamps) {                                                            \
-        st_acc[9] = L.fst[0];                                                               \
-        st_acc[10] = L.fst[1];                                                              \
-        st_acc[11] = L.fst[2];                                                              \
-        st_acc[8] = L.fst[3];                                                               \
-        st_acc[12] = L.fst[6];                                                              \
-        st_acc[13] = L.fst[7];                                                              \
-        for (int q_ = 0; q_ < kStampSlots; q_++)                                            \
-            atomicAdd((unsigned long long *)&g.stamps[((int64_t)img * 3 + (ph)-1) * kStampSlots + q_], \
-                      (unsigned long long)st_acc[q_]);                                      \
-    }
-#define FSTAMP_BEGIN const uint64_t fst_t0 = __builtin_amdgcn_s_memtime();
-// eval_ahead's sections on wave 0 (fst[6]: from the column loads to their data, fst[7]: the
-// forward query), with a vmcnt / lgkmcnt drain after the loads so the wait is attributed
-#define ESTAMP(L, i, t)                                                                     \
-    do {                                                                                    \
-        const uint64_t t_ = __builtin_amdgcn_s_memtime();                                   \
-        if ((threadIdx.x & 63) == 0) (L).fst[i] += t_ - (t);                                \
-        (t) = t_;                                                                           \
-    } while (0)
-#define FSTAMP_END(L, i)                                                                    \
-    if ((threadIdx.x & 63) == 0) (L).fst[i] += __builtin_amdgcn_s_memtime() - fst_t0;
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_FLUSH(ph)
-#define FSTAMP_BEGIN
-#define FSTAMP_END(L, i)
-#define ESTAMP(L, i, t)
-#endif
-constexpr int kStampSlots = 16;  // per (image, phase) in the diagnostic build
+#include "grow_device.hpp"
 
 namespace pp {
-
-constexpr int kKP = PP_MAX_KP;
-constexpr int kSlots = 2 * PP_MAX_EDGES;   // directed edges (two lanes' worth of slots)
-// flood-fill heap capacity: every joint is expanded at most once, pushing its by_source
-// entries, so a fill pushes at most 2C <= 2 * PP_MAX_EDGES entries
-constexpr int kHeap = 2 * PP_MAX_EDGES + 8;
-constexpr int kOccMargin = 64;              // NMS occupancy slack beyond the main grid
-constexpr int kCompleteWays = 64;           // force-complete workgroups per image
-
-struct FFEntry {  // _flood_fill frontier entry (-v, end_i, start_xyv, s)
-    float neg;
-    int end;
-    float sxyv[3];
-    float s;
-};
-
-struct OccLog {
-    int f;
-    int16_t x0, x1, y0, y1;
-};
-
-struct SeedExt;  // the seed loop's external-helper words (below)
-
-struct GrowArgs {
-    const pp_seed *seeds;
-    const int *seed_counts;
-    int seed_cap;
-    const float *cols[2];     // bucketed column sets (n_img, C, 2, kColRows, col_cap): set A
-                              // at caf_threshold, set B at complete_caf_threshold
-    const int *offs[2];       // bucket boundaries (n_img, C, 2, nb + 1)
-    int64_t col_cap;          // columns per set: the cells of all heads
-    // set B (force-complete, complete_caf_threshold) holds only concatenated cell indices
-    // (n_img, C, 2, col_cap); its queries read the heads' raw CAF and rescore with CifHr
-    // (consider_raw)
-    Heads heads;
-    HrMap hr;                 // CifHr (dense, or the tile-major scratch layout)
-    float cif_floor, one_minus_floor, th_b;
-    uint8_t caf_j1[PP_MAX_EDGES], caf_j2[PP_MAX_EDGES];  // 0-based joints of each CAF
-    int bw, bh, nb;           // bucket grid (see caf_bucketed_kernel)
-    float inv_e;
-    int K, C, hh, ww;
-    pp_config cfg;
-    // directed edges ("slots") in by_source order (cifcaf.py:62-65): joint j's entries
-    // are slots j_off[j] .. j_off[j+1]-1 in dict insertion order
-    int nd;
-    uint8_t j_off[kKP + 1];
-    uint8_t d_j[kSlots], d_k[kSlots], d_caf[kSlots], d_fwd[kSlots];
-    // CifCaf(confidence_scales=...) (cifcaf.py:259-260, 282-284): the slot's CAF weight on
-    // its frontier priorities when has_cs (pp_config.confidence_scales), else unused
-    int has_cs;
-    float slot_cs[kSlots];
-    // workspace (per image regions)
-    uint8_t *occ;
-    int64_t occ_cap;          // bytes per image
-    OccLog *log;
-    int log_cap;              // entries per image
-    pp_ann *work;             // working annotations
-    pp_ann *spec;             // (n_img, kSpecCache) speculatively grown annotations
-    float spec_far;           // seed-loop speculation distance, in joint scales
-    int n_ext;                // external helper workgroups per image (seed loop)
-    SeedExt *xext;            // (n_img) their hand-off words (zero at launch; the loop's last
-                              // workgroup out re-zeroes them, ext_exit)
-    pp_ann *xrec;             // (n_img, kExtCache) their published annotations
-    double *nms_score;        // (n_img, 2 * ann_cap)
-    // standalone NMS over caller annotations (pp_nms_keypoints_scored), else NULL: per
-    // (image, record) -2 fixed_score, -1 none, j >= 0 suppress_score_index; the record's
-    // score_weights (K each) and fixed scores (annotation.py:60-71)
-    const int32_t *nms_spec;
-    const double *nms_sw;
-    const double *nms_fixed;
-    double nms_it;            // nms.Keypoints.instance_threshold as the float64 it compares in
-    int *nms_idx;             // (n_img, 4 * ann_cap + ann_np)
-    float *nms_f;             // (n_img, 2 * ann_cap) per-annotation max x, max y
-    int2 *nms_box;            // (n_img, kNmsBoxLists, ann_cap) plane box lists beyond registers
-    int ann_np;               // next pow2 >= ann_cap
-    int ann_cap;
-    uint64_t *stamps;         // diagnostic build: (n_img, 3, kStampSlots) cycle sums, else NULL
-    int *n_work;              // (n_img) annotations after the seed loop (phase 1 -> 2)
-    int *complete_next;       // (n_img) force-complete work counters (zero region; the NMS
-                              // kernel, ordered after completion, resets them)
-    int *need_complete;       // (n_img) bitmask of joints left unset by the seed loop in any
-                              // annotation (force-complete has work iff != 0; gates the B sets)
-    // initial annotations (cifcaf.py:95-98), optional: (n_img, init_cap) records, the
-    // first init_counts[img] of an image grown and committed before its seed loop
-    const pp_ann *init;
-    const int *init_counts;
-    int init_cap;
-    // outputs
-    int *out_idx;             // optional (n_img, ann_cap): input index of each output record
-    pp_ann *out;
-    int *counts;
-    int *status;
-};
-
-// per-wave LDS of the grow kernels; HEAP: the flood-fill heap (force-complete only)
-template <bool HEAP>
-struct GrowLDST {
-    pp_ann a;                     // record being built (lists; data synced from registers)
-    FFEntry ff[HEAP ? kHeap : 1];
-    int mark_pre[kKP + 1];        // occupancy boxes of one annotation: area prefix
-    int mark_box[kKP][4];
-    int ff_n;
-    int log_n;
-    int status;
-#ifdef PP_STAMPS
-    uint64_t fst[10];  // inside-grow section sums (diagnostic build); [8], [9]: seed loop
-#endif
-};
-using GrowLDS = GrowLDST<true>;
-using SeedLDS = GrowLDST<false>;  // the seed loop's waves (no flood fill)
-
-
-__device__ __forceinline__ float rl_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ int rl_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-
-// Wave reductions on DPP (row-level VALU data movement, no LDS round trip): quad xor 1,
-// quad xor 2, row half-mirror, row mirror, then row_bcast15 / row_bcast31 fold the rows
-// into lane 63.  Each step pairs lanes holding disjoint lane sets, so any associative,
-// commutative merge (sum, min, exact top-2) is correct; lanes outside a step's row mask
-// receive `old` (the identity).
-constexpr int kDppXor1 = 0xB1;        // quad_perm [1,0,3,2]
-constexpr int kDppXor2 = 0x4E;        // quad_perm [2,3,0,1]
-constexpr int kDppHalfMirror = 0x141;
-constexpr int kDppMirror = 0x140;
-constexpr int kDppBcast15 = 0x142;
-constexpr int kDppBcast31 = 0x143;
-
-template <int CTRL, int ROWS>
-__device__ __forceinline__ int dpp_i(int old, int v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWS, 0xF, false);
-}
-template <int CTRL, int ROWS>
-__device__ __forceinline__ float dpp_f(float old, float v) {
-    return __int_as_float(
-        __builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROWS, 0xF, false));
-}
-
-// sum over the wave, uniform result
-__device__ __forceinline__ int wave_total(int v) {
-    v += dpp_i<kDppXor1, 0xF>(0, v);
-    v += dpp_i<kDppXor2, 0xF>(0, v);
-    v += dpp_i<kDppHalfMirror, 0xF>(0, v);
-    v += dpp_i<kDppMirror, 0xF>(0, v);
-    v += dpp_i<kDppBcast15, 0xA>(0, v);
-    v += dpp_i<kDppBcast31, 0xC>(0, v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// min over the wave (fminf: NaN ignored), uniform result
-__device__ __forceinline__ float wave_fmin(float v) {
-    v = fminf(v, dpp_f<kDppXor1, 0xF>(INFINITY, v));
-    v = fminf(v, dpp_f<kDppXor2, 0xF>(INFINITY, v));
-    v = fminf(v, dpp_f<kDppHalfMirror, 0xF>(INFINITY, v));
-    v = fminf(v, dpp_f<kDppMirror, 0xF>(INFINITY, v));
-    v = fminf(v, dpp_f<kDppBcast15, 0xA>(INFINITY, v));
-    v = fminf(v, dpp_f<kDppBcast31, 0xC>(INFINITY, v));
-    return rl_f(v, 63);
-}
 
 __device__ __forceinline__ bool ff_less(const FFEntry &a, const FFEntry &b) {
     if (a.neg != b.neg) return a.neg < b.neg;
@@ -561,12 +350,12 @@ __device__ void grow_connection_flat(const float *__restrict__ cf, int n, int64_
     finish_connection<MAXM>(t, out);
 }
 
+// diagnostic build: grow_connection's section sums into g.gc_stamps[img][4]
 #ifdef PP_STAMPS
-__device__ uint64_t *g_gc_stamps;  // diagnostic: [img][4] section sums of grow_connection
 #define GSTAMP(i)                                                                           \
     do {                                                                                    \
         const uint64_t t_ = __builtin_amdgcn_s_memtime();                                   \
-        if (lane == 0 && g_gc_stamps) atomicAdd((unsigned long long *)&g_gc_stamps[blockIdx.x * 4 + (i)], (unsigned long long)(t_ - gs_t));        \
+        if (lane == 0 && g.gc_stamps) atomicAdd((unsigned long long *)&g.gc_stamps[blockIdx.x * 4 + (i)], (unsigned long long)(t_ - gs_t));        \
         gs_t = t_;                                                                          \
     } while (0)
 #else
@@ -580,9 +369,7 @@ __device__ __forceinline__ void grow_connection(const GrowArgs &g, const float *
                                 const int *__restrict__ off, float x, float y, float xy_scale,
                                 float out[4]) {
     const int lane = threadIdx.x & 63;
-#ifdef PP_STAMPS
-    uint64_t gs_t = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_T0(gs_t);
     const int64_t hw = g.col_cap;
     const ColQuery q = make_query(x, y, xy_scale, g.cfg.exp_mode);
     Top2 t = top2_empty();
@@ -974,9 +761,7 @@ __device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int i
     r0 &= ss.small[0];  // the others stay lazy
     r1 &= ss.small[1];
     while (r0 | r1) {
-#ifdef PP_STAMPS
-        uint64_t et = __builtin_amdgcn_s_memtime();
-#endif
+        STAMP_T0(et);
         int sl[kAhead];
 #pragma unroll
         for (int b = 0; b < kAhead; b++) {  // the next kAhead slots
@@ -1008,10 +793,8 @@ __device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int i
             flat_load_set(col_set(g, 0, img, caf, 1 - df), hw, nb[b], cs.lds, (pb & 0xFFFF) - 1,
                           vb[b]);
         }
-#ifdef PP_STAMPS
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        STAMP_DO(asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"));
         ESTAMP(L, 6, et);
-#endif
 #pragma unroll
         for (int b = 0; b < kAhead; b++) {
             if (sl[b] < 0) continue;
@@ -1019,9 +802,7 @@ __device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int i
             const float jx = rl_f(ax, j), jy = rl_f(ay, j), jv = rl_f(av, j), js = rl_f(as, j);
             float nx[4];
             flat_query<MAXM>(vf[b], nf[b], jx, jy, max0(js), g.cfg.exp_mode, nx);
-#ifdef PP_STAMPS
             ESTAMP(L, 7, et);
-#endif
             float res[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             const float ks = sqrtf(nx[3] * jv);
             if (!(ks < g.cfg.keypoint_threshold) && nx[3] != 0.0f) {
@@ -1147,9 +928,7 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
                 nx[2] = e.ps;
                 nx[3] = e.pv;
             } else {
-#ifdef PP_STAMPS
-                if (lane == 0) L.fst[3] += 1;
-#endif
+                STAMP_DO(if (lane == 0) L.fst[3] += 1);
                 FSTAMP_BEGIN
                 connection_value(g, img, set, e.caf, e.fwd, rl_f(ax, e.j), rl_f(ay, e.j),
                                  rl_f(av, e.j), rl_f(as, e.j), reverse_match, nx);
@@ -1262,66 +1041,6 @@ __device__ __forceinline__ void flood_fill(const GrowArgs &g, GrowLDS &L) {  // 
         L.a.joint_scales[end_i] = top.s;
         add(end_i, top.sxyv[2]);
     }
-}
-
-// ---------------------------------------------------------------------------------------
-// occupancy (occupancy.py:10-47, decoder/utils.py:61-66)
-// ---------------------------------------------------------------------------------------
-// u8 planes (f, h, w) stored with a row pitch of round_up(w, 16) bytes, so that no two
-// rows (and no two planes) share a 16-byte chunk: marking updates whole chunks.
-struct OccGrid {
-    uint8_t *p;
-    int f, h, w, pitch;
-};
-
-__device__ __forceinline__ OccGrid occ_grid(uint8_t *p, int f, int h, int w) {
-    return OccGrid{p, f, h, w, (w + 15) & ~15};
-}
-
-__device__ __forceinline__ long round_half_even(float x) { return (long)rintf(x); }
-
-// Occupancy.get (occupancy.py:41-47): nonzero at floor((x, y) / reduction), clipped
-__device__ __forceinline__ bool occ_get(const OccGrid &o, int f, float x, float y, float red) {
-    if (f >= o.f) return true;
-    if (o.h <= 0 || o.w <= 0) return false;  // the reference reads out of bounds here
-    x = clip_ref(x / red, 0.0f, (float)(o.w - 1));
-    y = clip_ref(y / red, 0.0f, (float)(o.h - 1));
-    const int xi = (int)x, yi = (int)y;
-    return o.p[((int64_t)f * o.h + yi) * o.pitch + xi] != 0;
-}
-
-// Occupancy.set box (occupancy.py:31-39 + utils.py:61-66) of joint f; false when empty.
-// red = reduction, msr = min_scale / reduction (occ_box below takes them from the config)
-__device__ __forceinline__ bool occ_box_r(float red, float msr, const OccGrid &o, int f, float x,
-                                          float y, float sigma, int box[4]) {
-    if (f >= o.f) return false;
-    const long xi = (long)rintf(x / red);  // round(): half to even
-    const long yi = (long)rintf(y / red);
-    const float sr = sigma / red;
-    const long si = (long)rintf((sr > msr) ? sr : msr);  // max(min_scale_reduced, sigma / r)
-    const long minx = xi - si > 0 ? xi - si : 0;
-    const long miny = yi - si > 0 ? yi - si : 0;
-    const long mx = xi + si + 1 < o.w ? xi + si + 1 : o.w;
-    const long my = yi + si + 1 < o.h ? yi + si + 1 : o.h;
-    long maxx = minx + 1 > mx ? minx + 1 : mx;
-    long maxy = miny + 1 > my ? miny + 1 : my;
-    if (maxx > o.w) maxx = o.w;  // numpy slice clipping
-    if (maxy > o.h) maxy = o.h;
-    if (minx >= maxx || miny >= maxy) return false;
-    box[0] = (int)minx;
-    box[1] = (int)maxx;
-    box[2] = (int)miny;
-    box[3] = (int)maxy;
-    return true;
-}
-
-__device__ __forceinline__ float occ_msr(const GrowArgs &g) {
-    return (float)((double)g.cfg.occupancy_min_scale / g.cfg.occupancy_reduction);
-}
-
-__device__ __forceinline__ bool occ_box(const GrowArgs &g, const OccGrid &o, int f, float x, float y, float sigma,
-                        int box[4]) {
-    return occ_box_r((float)g.cfg.occupancy_reduction, occ_msr(g), o, f, x, y, sigma, box);
 }
 
 // Mark the boxes of every joint j with mark(j) in one pass: joints live on different
@@ -1538,102 +1257,6 @@ __device__ __forceinline__ void occ_clear(const GrowArgs &g, LDS &L, OccLog *log
     wave_sync();
 }
 
-// np.sum of K float64 terms in NumPy's pairwise order (n <= 128: eight accumulators over
-// blocks of 8, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail)
-__device__ double pw_sum(const double *a, int K) {
-    if (K < 8) {
-        double res = 0.0;
-        for (int i = 0; i < K; i++) res += a[i];
-        return res;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i;
-    for (i = 8; i < K - (K % 8); i += 8) {
-        r0 += a[i];
-        r1 += a[i + 1];
-        r2 += a[i + 2];
-        r3 += a[i + 3];
-        r4 += a[i + 4];
-        r5 += a[i + 5];
-        r6 += a[i + 6];
-        r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < K; i++) res += a[i];
-    return res;
-}
-
-// all loads first, then all stores: one round trip (the two records may alias as far as the
-// compiler knows, so a plain copy loop waits for every load in turn)
-// a record copy in two halves, so that other work overlaps the loads' latency: the loads
-// into registers (per lane kAnnWords words), then the stores
-constexpr int kAnnWords = (int)((sizeof(pp_ann) / 4 + 63) / 64);
-struct AnnRegs {
-    uint32_t v[kAnnWords];
-};
-__device__ __forceinline__ AnnRegs ann_load(const pp_ann *src) {
-    const uint32_t *s = reinterpret_cast<const uint32_t *>(src);
-    constexpr int nw = sizeof(pp_ann) / 4;
-    const int lane = threadIdx.x & 63;
-    AnnRegs r;
-#pragma unroll
-    for (int u = 0; u < kAnnWords; u++) r.v[u] = (u * 64 + lane < nw) ? s[u * 64 + lane] : 0u;
-    return r;
-}
-__device__ __forceinline__ void ann_store(pp_ann *dst, const AnnRegs &r) {
-    uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-    constexpr int nw = sizeof(pp_ann) / 4;
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int u = 0; u < kAnnWords; u++)
-        if (u * 64 + lane < nw) d[u * 64 + lane] = r.v[u];
-    wave_sync();
-}
-
-__device__ __forceinline__ void copy_ann(pp_ann *dst, const pp_ann *src) {
-    const uint32_t *s = reinterpret_cast<const uint32_t *>(src);
-    uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-    constexpr int nw = sizeof(pp_ann) / 4;
-    constexpr int per = (nw + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    uint32_t v[per];
-#pragma unroll
-    for (int u = 0; u < per; u++) v[u] = (u * 64 + lane < nw) ? s[u * 64 + lane] : 0u;
-#pragma unroll
-    for (int u = 0; u < per; u++)
-        if (u * 64 + lane < nw) d[u * 64 + lane] = v[u];
-    wave_sync();
-}
-
-// stable sort of idx[0..n) by descending score (sorted(anns, key=lambda a: -a.score()))
-__device__ void sort_by_score(int *perm, int np, int n, const double *score) {
-    for (int i = threadIdx.x & 63; i < np; i += 64) perm[i] = i;
-    wave_sync();
-    for (int k = 2; k <= np; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x & 63; i < np; i += 64) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const int a = perm[i], b = perm[ixj];
-                    auto before = [&](int p, int q) {
-                        if (p >= n) return false;
-                        if (q >= n) return true;
-                        const double kp = -score[p], kq = -score[q];
-                        if (kp != kq) return kp < kq;
-                        return p < q;
-                    };
-                    const bool asc = (i & k) == 0;
-                    if (asc ? before(b, a) : before(a, b)) {
-                        perm[i] = b;
-                        perm[ixj] = a;
-                    }
-                }
-            }
-            wave_sync();
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------
 // seed loop (cifcaf.py:84-108): one workgroup of kSeedWaves waves per image
 // ---------------------------------------------------------------------------------------
@@ -1653,14 +1276,7 @@ __device__ void sort_by_score(int *perm, int np, int n, const double *score) {
 // to grow one itself, and a helper publishes its annotation (cache slot state 2) whenever
 // it finishes.  Wave 0 waits on a helper only for the seed it needs next, if that helper
 // is still growing it.  The handshake is LDS flags with workgroup-scope acquire/release.
-// 8 waves; 16 (cache 32, scan 256): 1.79 vs 1.28 ms per cfg3 step; 4 / 6: no better
-constexpr int kSeedWaves = 8;
-constexpr int kSpecCache = 16;     // speculative annotations of this CU's helpers
 constexpr int kSpecScan = 128;     // seeds after the committed one examined per round
-// distance (joint scales) a helper's seed keeps from the committed one and from the
-// round's other picks; cached annotations are excluded by their exact occupancy boxes.
-// Throughput is flat for 0-4 (both generators) and drops beyond 8.
-constexpr float kSpecFar = 4.0f;
 constexpr int kSelfScan = 256;     // seeds after the decided ones a finished helper examines
 // seeds after the committed one that wave 0 of seed_loop_ext_kernel examines per plan round
 // (cfg5 planted 42.9k-43.7k -> 45.8k-47.0k images/s with 512 instead of 128, round 6)
@@ -1714,11 +1330,6 @@ constexpr int kExtRefill = 12;
 // 1 -> 3; losing that CAS to an assignment means: grow it).  The image's workgroups count
 // themselves out (SeedExt.exited) after their last access to these words, and the last one
 // out zeroes them, so every launch finds them zero whatever runs between two seed loops.
-constexpr int kExtWgMax = 3;
-constexpr int kExtHelpers = kExtWgMax * kSeedWaves;
-constexpr int kExtCache = 32;
-constexpr int kCacheSlots = kSpecCache + kExtCache;  // one lane per slot
-static_assert(kCacheSlots <= 64 && kSeedWaves + kExtHelpers <= 64, "one lane per slot / helper");
 // Policy (s_memrealtime ticks, 100 MHz).  Wave 0 waits for an external slot it needs next
 // only if that grow is at least half done by the running mean of external grows (at most
 // 2 s: a helper always finishes); otherwise it grows the seed itself and the slot is a
@@ -1735,18 +1346,6 @@ constexpr uint64_t kExtWaitMax = 200000000ull;
 // (Wave 0 planning the idle helpers while it waits for one, once per wait, when that grow is
 // expected to run 40 us longer on images of 32+ annotations: cfg5 uniform 1445-1724 vs
 // 1670 images/s without, planted 39.8-41.2k vs 40.4-43.5k, round 6.)
-
-struct SeedExt {  // per image; zero at every launch (workspace zero region; the launch's
-                  // last workgroup out re-zeroes it, ext_exit)
-    unsigned long long task[kExtHelpers];  // 0 absent, 1 idle, 3 left; assigned: 2 |
-                                           // slot << 8 | seed << 32
-    unsigned int tag[kExtCache];           // seed + 1 of the record published in the slot
-    unsigned int fin;                      // wave 0 is done
-    unsigned int heavy;                    // wave 0 switched to the heavy regime
-    unsigned int exited;                   // workgroups of the image done with these words
-    unsigned int pad;
-};
-static_assert(sizeof(SeedExt) % 16 == 0, "memset block of whole 16-byte units");
 
 typedef __attribute__((address_space(1))) unsigned int gu32;
 typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -2249,9 +1848,7 @@ void seed_loop_kernel(GrowArgs g) {
     if (lane == 0) {
         L.status = 0;
         L.log_n = 0;
-#ifdef PP_STAMPS
-        for (int q = 0; q < 10; q++) L.fst[q] = 0;
-#endif
+        STAMP_DO(for (int q = 0; q < 10; q++) L.fst[q] = 0);
     }
     if (threadIdx.x < kSpecCache) {
         S.cache_seed[threadIdx.x] = -1;
@@ -2292,18 +1889,14 @@ void seed_loop_kernel(GrowArgs g) {
     // committer state (wave 0)
     int n_anns = 0, s = 0;
     uint32_t unset_mask = 0;
-#ifdef PP_STAMPS
-    int n_rounds = 0, n_hits = 0;
-#endif
+    STAMP_DO(int n_rounds = 0, n_hits = 0);
 
     // append one finished annotation and mark_occupied (cifcaf.py:87-93): wave 0 only
     // (lane j < K holds joint j of the record: x, y, v, scale, from LDS)
     // (the record's loads are issued first and stored after the marks: the marks hide
     // their latency)
     auto commit = [&](const pp_ann *src, float jx, float jy, float jv, float js) {
-#ifdef PP_STAMPS
-        uint64_t ct0 = __builtin_amdgcn_s_memtime();
-#endif
+        STAMP_T0(ct0);
         const AnnRegs rec = ann_load(src);
         const uint32_t set = (uint32_t)__ballot(lane < K && jv > 0.0f);
         unset_mask |= ~set & (K >= 32 ? 0xFFFFFFFFu : ((1u << K) - 1u));
@@ -2311,14 +1904,10 @@ void seed_loop_kernel(GrowArgs g) {
             seed_occ_mark(g, s_occ, occ, jx, jy, js, jv != 0.0f, K);
         else
             occ_mark(g, L, log, occ, jx, jy, js, jv != 0.0f, K);
-#ifdef PP_STAMPS
         ESTAMP(L, 5, ct0);  // (wave 0) the occupancy marks
-#endif
         ann_store(&work[n_anns], rec);
         n_anns++;
-#ifdef PP_STAMPS
         ESTAMP(L, 4, ct0);  // (wave 0) the record's stores (after the marks)
-#endif
     };
 
     if (wave > 0) {  // helper: grow the seeds wave 0 hands over until it is done
@@ -2333,9 +1922,7 @@ void seed_loop_kernel(GrowArgs g) {
                 my = lds_acquire(&S.task[wave]);
                 if (my >= 0 || lds_acquire(&S.done)) break;
                 if (idle_dec >= 0 && lds_acquire(&S.decided) != idle_dec) {
-#ifdef PP_STAMPS
-                    const uint64_t hp2 = __builtin_amdgcn_s_memtime();
-#endif
+                    STAMP_T0(hp2);
                     plan_lock(S);
                     uint64_t left = 1ull << wave;
                     const int dec = lds_acquire(&S.decided);
@@ -2344,17 +1931,13 @@ void seed_loop_kernel(GrowArgs g) {
                                          left, socc);
                     plan_unlock(S);
                     idle_dec = left ? dec : -1;
-#ifdef PP_STAMPS
-                    if (lane == 0) L.fst[8] += __builtin_amdgcn_s_memtime() - hp2;
-#endif
+                    STAMP_DO(if (lane == 0) L.fst[8] += STAMP_SINCE(hp2));
                     continue;
                 }
                 if (lds_acquire(&S.plan_req)) {
                     // wave 0 is growing a seed of its own: plan every idle helper (this one
                     // included) around it
-#ifdef PP_STAMPS
-                    const uint64_t hp0 = __builtin_amdgcn_s_memtime();
-#endif
+                    STAMP_T0(hp0);
                     plan_lock(S);
                     if (lds_acquire(&S.plan_req) && !lds_acquire(&S.done)) {
                         if (lane == 0) lds_release(&S.plan_req, 0);
@@ -2367,35 +1950,27 @@ void seed_loop_kernel(GrowArgs g) {
                     }
                     plan_unlock(S);
                     if (lds_acquire(&S.task[wave]) < 0) idle_dec = lds_acquire(&S.decided);
-#ifdef PP_STAMPS
-                    if (lane == 0) L.fst[8] += __builtin_amdgcn_s_memtime() - hp0;
-#endif
+                    STAMP_DO(if (lane == 0) L.fst[8] += STAMP_SINCE(hp0));
                     continue;
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
             if (my < 0) break;
             const int q = S.task_slot[wave];
-#ifdef PP_STAMPS
-            const uint64_t hg0 = __builtin_amdgcn_s_memtime();
-#endif
+            STAMP_T0(hg0);
             ann_from_seed(L, seeds[my], K, img);
             grow<true, CS>(g, L, img, 0, true, cstage, &S.done, S.cache_j[q], &S.cache_pm[q]);
-#ifdef PP_STAMPS
-            if (lane == 0) {  // helper grows and their cycles (phase-1 slots 8 and 5)
+            STAMP_DO(if (lane == 0) {  // helper grows and their cycles (phase-1 slots 8 and 5)
                 L.fst[4] += 1;
-                L.fst[5] += __builtin_amdgcn_s_memtime() - hg0;
-            }
-#endif
+                L.fst[5] += STAMP_SINCE(hg0);
+            });
             if (lds_acquire(&S.done)) break;  // nobody reads the cache any more
             if (lane < kKP)
                 S.cache_box[q][lane] = plan_box(
                     red, msr, occ, lane,
                     make_float4(L.a.data[lane][0], L.a.data[lane][1], L.a.data[lane][2], L.a.joint_scales[lane]));
             publish_cached(S, cache, q, L);  // (its release orders the boxes too)
-#ifdef PP_STAMPS
-            const uint64_t hp1 = __builtin_amdgcn_s_memtime();
-#endif
+            STAMP_T0(hp1);
             // plan this wave's next grow itself, with its own annotation now in the cache (its
             // occupancy boxes rule out the other seeds of the same person); wave 0 plans only
             // when it has to grow a seed itself
@@ -2409,12 +1984,10 @@ void seed_loop_kernel(GrowArgs g) {
             if (left && lane == 0) lds_release(&S.task[wave], -1);
             plan_unlock(S);
             idle_dec = left ? lds_acquire(&S.decided) : -1;
-#ifdef PP_STAMPS
-            if (lane == 0) {
-                L.fst[8] += __builtin_amdgcn_s_memtime() - hp1;
+            STAMP_DO(if (lane == 0) {
+                L.fst[8] += STAMP_SINCE(hp1);
                 L.fst[9] += 1;
-            }
-#endif
+            });
         }
     } else {
         __builtin_amdgcn_s_setprio(3);  // the committer is the critical path: issue first
@@ -2433,20 +2006,14 @@ void seed_loop_kernel(GrowArgs g) {
             const uint64_t hit = __ballot(lane < kSpecCache && cs == t);
             if (hit) {  // a helper grew it, or is growing it
                 const int slot = __ffsll((unsigned long long)hit) - 1;
-#ifdef PP_STAMPS
-                const uint64_t hw0 = __builtin_amdgcn_s_memtime();
-#endif
+                STAMP_T0(hw0);
                 while (lds_acquire(&S.cache_state[slot]) != 2) __builtin_amdgcn_s_sleep(1);
-#ifdef PP_STAMPS
-                if (lane == 0) L.fst[8] += __builtin_amdgcn_s_memtime() - hw0;
-#endif
+                STAMP_DO(if (lane == 0) L.fst[8] += STAMP_SINCE(hw0));
                 const float4 jq = lane < kKP ? S.cache_j[slot][lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 commit(&cache[slot], jq.x, jq.y, jq.z, jq.w);
                 s = t + 1;
                 if (lane == 0) lds_release(&S.decided, s);  // the slot is free again
-#ifdef PP_STAMPS
-                n_hits++;
-#endif
+                STAMP_DO(n_hits++);
                 STAMP(4);
                 continue;
             }
@@ -2463,9 +2030,7 @@ void seed_loop_kernel(GrowArgs g) {
                 lds_release(&S.plan_req, 1);
             }
             wave_sync();
-#ifdef PP_STAMPS
-            n_rounds++;
-#endif
+            STAMP_DO(n_rounds++);
             STAMP(1);
             ann_from_seed(L, st, K, img);
             grow<true, CS>(g, L, img, 0, true, cstage, nullptr, S.own_j, &S.own_pm);
@@ -2535,9 +2100,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
     if (lane == 0) {
         L.status = 0;
         L.log_n = 0;
-#ifdef PP_STAMPS
-        for (int q = 0; q < 10; q++) L.fst[q] = 0;
-#endif
+        STAMP_DO(for (int q = 0; q < 10; q++) L.fst[q] = 0);
     }
     if (threadIdx.x < NS) {
         S.cache_seed[threadIdx.x] = -1;
@@ -2576,9 +2139,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
     // committer state (wave 0)
     int n_anns = 0, s = 0;
     uint32_t unset_mask = 0;
-#ifdef PP_STAMPS
-    int n_rounds = 0, n_hits = 0;
-#endif
+    STAMP_DO(int n_rounds = 0, n_hits = 0);
 
     // append one finished annotation and mark_occupied (cifcaf.py:87-93): wave 0 only
     // (lane j < K holds joint j of the record: x, y, v, scale, from LDS)
@@ -2666,13 +2227,9 @@ void seed_loop_ext_kernel(GrowArgs g) {
         // ones), with S.plan_lock held; `own`: wave 0 grows seed st itself next (the picks
         // keep kSpecFar from it too)
         auto plan_round = [&](const int t, const bool own, const pp_seed &st) {
-#ifdef PP_STAMPS
-            const uint64_t xr0 = __builtin_amdgcn_s_memtime();
-#endif
+            STAMP_T0(xr0);
             ext_refresh(S, s_cols, X, xrec, -1, red, msr, occ);
-#ifdef PP_STAMPS
-            st_acc[14] += __builtin_amdgcn_s_memtime() - xr0;  // plan: the external slots' refresh
-#endif
+            STAMP_DO(st_acc[14] += STAMP_SINCE(xr0));  // plan: the external slots' refresh
             int tk = 0;
             if (lane > 0 && lane < kSeedWaves)
                 tk = lds_acquire(&S.task[lane]) < 0 ? 1 : 0;
@@ -2690,9 +2247,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
             // the seeds in flight: later picks keep kSpecFar from them
             uint64_t fly = __ballot(sl && r_st == 1);
             const int scan_end = min(n_seeds, t + 1 + kExtScan);
-#ifdef PP_STAMPS
-            uint64_t pf0 = __builtin_amdgcn_s_memtime();
-#endif
+            STAMP_T0(pf0);
             for (int base = t + 1; base < scan_end && idle; base += 64) {
                 const int idx = base + lane;
                 bool ok = idx < scan_end;
@@ -2736,9 +2291,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
                             ok = false;
                 }
                 uint64_t m = __ballot(ok);
-#ifdef PP_STAMPS
                 ESTAMP(L, 6, pf0);  // plan: the seed filter
-#endif
                 while (m && idle) {
                     const int l = __ffsll((unsigned long long)m) - 1;
                     m &= m - 1;
@@ -2768,13 +2321,9 @@ void seed_loop_ext_kernel(GrowArgs g) {
                     if (!use_l) {  // the helper may have just left: then skip it
                         const unsigned long long job = 2ull | ((unsigned long long)(q - kSpecCache) << 8) |
                                                        ((unsigned long long)sd << 32);
-#ifdef PP_STAMPS
-                        const uint64_t xc0 = __builtin_amdgcn_s_memtime();
-#endif
+                        STAMP_T0(xc0);
                         const bool got = cas_agent_wave(&X->task[w - kSeedWaves], 1ull, job);
-#ifdef PP_STAMPS
-                        st_acc[15] += __builtin_amdgcn_s_memtime() - xc0;  // plan: hand-off CAS
-#endif
+                        STAMP_DO(st_acc[15] += STAMP_SINCE(xc0));  // plan: hand-off CAS
                         if (!got) {
                             m |= 1ull << l;  // the seed is still unassigned
                             continue;
@@ -2802,9 +2351,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
                     }
                     wave_sync();
                 }
-#ifdef PP_STAMPS
                 ESTAMP(L, 6, pf0);  // plan: the picks
-#endif
             }
         };
         for (;;) {
@@ -2825,9 +2372,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
             int hslot = -1;
             if (hit) {  // a helper grew it, or is growing it
                 const int slot = __ffsll((unsigned long long)hit) - 1;
-#ifdef PP_STAMPS
-                uint64_t hw0 = __builtin_amdgcn_s_memtime();
-#endif
+                STAMP_T0(hw0);
                 if (slot < kSpecCache) {
                     while (lds_acquire(&S.cache_state[slot]) != 2) __builtin_amdgcn_s_sleep(1);
                 } else {
@@ -2850,9 +2395,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
                 }
                 taken = S.cache_state[slot] == 2;
                 hslot = slot;
-#ifdef PP_STAMPS
                 ESTAMP(L, 7, hw0);  // a hit: waiting for the helper
-#endif
             }
             if (taken) {
                 const float4 jq = lane < kKP ? cache_joints(S, s_cols, hslot)[lane]
@@ -2863,9 +2406,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
                     commit(&xrec[hslot - kSpecCache], true, jq.x, jq.y, jq.z, jq.w);
                 s = t + 1;
                 if (lane == 0) lds_release(&S.decided, s);  // the slot is free again
-#ifdef PP_STAMPS
-                n_hits++;
-#endif
+                STAMP_DO(n_hits++);
                 if (n_anns >= kExtRefillAnns) {
                     // few speculated seeds left ahead: plan a round now, not at the next miss
                     const uint64_t aq = __ballot(lane < NS && S.cache_seed[lane] > t &&
@@ -2895,9 +2436,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
             // r06z_ab_refill.txt)
             plan_round(t, false, st);
             plan_unlock(S);
-#ifdef PP_STAMPS
-            n_rounds++;
-#endif
+            STAMP_DO(n_rounds++);
             STAMP(1);
             ann_from_seed(L, st, K, img);
             grow<true, CS>(g, L, img, 0, true, cstage);
@@ -2922,10 +2461,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
     if (wave == 0) {
         occ_clear(g, L, log, occ);
         STAMP(5);
-#ifdef PP_STAMPS
-        st_acc[6] = n_rounds;
-        st_acc[7] = n_hits;
-#endif
+        STAMP_DO(st_acc[6] = n_rounds; st_acc[7] = n_hits);
         STAMP_FLUSH(1);
         seed_loop_outputs(g, Ls, img, n_anns, unset_mask);
     }
@@ -2949,9 +2485,7 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
     if (lane == 0) {
         L.status = 0;
         L.log_n = 0;
-#ifdef PP_STAMPS
-        for (int q = 0; q < 8; q++) L.fst[q] = 0;
-#endif
+        STAMP_DO(for (int q = 0; q < 8; q++) L.fst[q] = 0);
     }
     wave_sync();
     STAMP_DECL
@@ -2988,1231 +2522,49 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
     if (lane == 0 && L.status) atomicOr(&g.status[img], L.status);
 }
 
-// ---- nms.Keypoints.annotations (nms.py:17-57) + output, one workgroup per image ----
-// The score filters are per annotation: spread over the waves.  The suppression pass
-// (nms.py:34-45) is sequential over the sorted annotations, but each joint lives on its
-// own occupancy plane, so the planes are independent: wave w walks planes w, w + 8, ...
-// and keeps the plane's marked boxes in a list instead of a u8 grid.  A joint is
-// "occupied" iff the number of earlier marked boxes covering its cell is non-zero mod 256
-// (the grid's u8 += 1 wraps), which is exactly what the grid lookup returns.
-// Workgroups of kNmsWaves (8) waves for dense batches on the one-CU seed loop
-// (PP_STAGE_NMS_WIDE), else kNmsNarrow (4): at 155 VGPRs a 4-wave workgroup (one wave per
-// SIMD) fits on a CU beside a seed-loop workgroup (two waves per SIMD at 168), an 8-wave one
-// does not, so in the overlapped pipeline the narrow NMS of batch i runs beside batch i + 1's
-// seed loop instead of waiting for its CUs.  A/B on one box: planted cfg3 370-375k ->
-// 385-394k images/s, cfg5 uniform 1356-1365 -> 1434-1443; uniform cfg3 (400 annotations per
-// image, 17 planes on 4 waves) 15.1-15.3k -> 14.4-14.5k, hence the wide form there.
-constexpr int kNmsWaves = 8;
-constexpr int kNmsNarrow = 4;
-// box-list scratch per image: one list per wave of nms_kernel, or per plane of
-// nms_planes_kernel's fallback
-constexpr int kNmsBoxLists = PP_MAX_KP;
-static_assert(kNmsBoxLists >= kNmsWaves, "one box list per NMS wave");
-// boxes per plane kept in REGISTERS, kNmsRegBoxes per lane (box i: lane i % 64, slot
-// i / 64), global scratch beyond: a check is ALU over the lane's slots plus one wave sum,
-// and the kernel needs no LDS for them (it fits beside the seed loop's 104 KB).  With the
-// list in LDS (448 per plane) and global memory beyond, uniform cfg5 (1370 annotations per
-// image) spent 20M cycles per image in the suppression pass on global-list loads.
-constexpr int kNmsRegBoxes = 24;
+}  // namespace pp
 
-struct ScoreLDS {
-    double prod[kKP];
-    double score_bc;
-#ifdef PP_STAMPS
-    uint64_t fst[8];  // unused here; keeps STAMP_FLUSH uniform
-#endif
-};
+// ---------------------------------------------------------------------------------------
+// host: the launchers of the kernels above (decode.hip has the rest of the host side)
+// ---------------------------------------------------------------------------------------
+namespace pp {
 
-// Annotation.score() (annotation.py:24-28, 60-71) in float64, collective over one wave:
-// lane j finds the rank of v_j in descending order, the rank-ordered products go to LDS
-// and lane 0 adds them in NumPy's pairwise order.  `zero_j` (suppress_score_index, >= 0)
-// reads as v = 0; `w` (the record's own score_weights) replaces the default weights.
-__device__ double ann_score_w(ScoreLDS &L, const float (*data)[3], int K, int zero_j = -1,
-                              const double *w = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const double ws = (double)(3 * min(K, 3) + (K - min(K, 3)));
-    if (lane < K) {
-        const float vj = lane == zero_j ? 0.0f : data[lane][2];
-        int rank = 0;
-        for (int i = 0; i < K; i++) {
-            const float vi = i == zero_j ? 0.0f : data[i][2];
-            rank += (vi > vj) || (vi == vj && i < lane);
-        }
-        L.prod[rank] = (w ? w[rank] : (rank < 3 ? 3.0 : 1.0) / ws) * (double)vj;
-    }
-    wave_sync();
-    if (lane == 0) L.score_bc = pw_sum(L.prod, K);
-    wave_sync();
-    const double res = L.score_bc;
-    wave_sync();
-    return res;
-}
-
-// the score nms.Keypoints sorts and filters record i of image img by: the default
-// Annotation.score(), or with the caller's per-record fixed_score / suppress_score_index /
-// score_weights (standalone NMS)
-__device__ double nms_ann_score(const GrowArgs &g, ScoreLDS &L, int img, int i,
-                                const float (*data)[3], int K) {
-    if (!g.nms_spec) return ann_score_w(L, data, K);
-    const int64_t gi = (int64_t)img * g.ann_cap + i;
-    const int spec = g.nms_spec[gi];
-    if (spec == -2) return g.nms_fixed[gi];
-    return ann_score_w(L, data, K, spec, g.nms_sw + gi * K);
-}
-
-// the grid cell occ_get reads: 1 = occupied whatever the grid holds (f beyond the planes),
-// 0 = free whatever it holds (empty grid), -1 = look at (xi, yi)
-__device__ __forceinline__ int occ_cell(const OccGrid &o, int f, float x, float y, float red,
-                                        int &xi, int &yi) {
-    if (f >= o.f) return 1;
-    if (o.h <= 0 || o.w <= 0) return 0;
-    xi = (int)clip_ref(x / red, 0.0f, (float)(o.w - 1));
-    yi = (int)clip_ref(y / red, 0.0f, (float)(o.h - 1));
-    return -1;
-}
-
-// nms.py:34-45 for plane f: the m kept annotations in sorted order, whose joint f
-// `load(r0, wi, x, y, v, s)` gives per lane (annotation r0 + lane: work index, joint f; v = 0
-// beyond m).  The plane's marked boxes are kept in a list instead of a u8 grid: kNmsRegBoxes
-// per lane in registers, `gbox` beyond.  A joint is "occupied" iff the number of earlier
-// marked boxes covering its cell is non-zero mod 256 (the grid's u8 += 1 wraps).  Suppressed
-// joints are written (v * suppression) as they are found.
-template <typename Load>
-__device__ __forceinline__ void nms_plane_boxes(const GrowArgs &g, pp_ann *work, int m, int f,
-                                                const OccGrid &no, float red, int2 *gbox,
-                                                Load load) {
-    const int lane = threadIdx.x & 63;
-    int nbox = 0;
-    int2 rb[kNmsRegBoxes];  // (x0 | x1 << 16, y0 | y1 << 16); zero: covers nothing
-#pragma unroll
-    for (int q = 0; q < kNmsRegBoxes; q++) rb[q] = make_int2(0, 0);
-    for (int r0 = 0; r0 < m; r0 += 64) {
-        int wi = 0;
-        float jx = 0.0f, jy = 0.0f, jv = 0.0f, js = 0.0f;
-        load(r0, wi, jx, jy, jv, js);
-        const int nr = min(64, m - r0);
-        for (int l = 0; l < nr; l++) {
-            const float v = rl_f(jv, l);
-            if (v == 0.0f) continue;
-            const float x = rl_f(jx, l), y = rl_f(jy, l);
-            int xi = 0, yi = 0;
-            const int fixed = occ_cell(no, f, x, y, red, xi, yi);
-            int cnt = 0;
-            if (fixed < 0) {
-#pragma unroll
-                for (int q = 0; q < kNmsRegBoxes; q += 4) {  // unused slots are zero
-                    if (q * 64 >= nbox) continue;  // uniform: skip empty groups
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int2 b = rb[q + u];
-                        cnt += (xi >= (b.x & 0xFFFF) && xi < (b.x >> 16) &&
-                                yi >= (b.y & 0xFFFF) && yi < (b.y >> 16));
-                    }
-                }
-                for (int q = kNmsRegBoxes * 64 + lane; q < nbox; q += 64) {
-                    const int2 b = gbox[q];
-                    cnt += (xi >= (b.x & 0xFFFF) && xi < (b.x >> 16) &&
-                            yi >= (b.y & 0xFFFF) && yi < (b.y >> 16));
-                }
-                cnt = wave_total(cnt);
-            }
-            const bool occupied = fixed < 0 ? (cnt & 255) != 0 : fixed == 1;
-            if (occupied) {
-                if (lane == 0) work[rl_i(wi, l)].data[f][2] = v * g.cfg.nms_suppression;
-            } else {
-                int box[4];
-                if (occ_box(g, no, f, x, y, rl_f(js, l), box)) {
-                    const int2 nb = make_int2(box[0] | (box[1] << 16), box[2] | (box[3] << 16));
-                    if (nbox < kNmsRegBoxes * 64) {
-#pragma unroll
-                        for (int q = 0; q < kNmsRegBoxes; q++)
-                            if (q == (nbox >> 6) && lane == (nbox & 63)) rb[q] = nb;
-                    } else if (lane == 0) {
-                        gbox[nbox] = nb;
-                    }
-                    nbox++;
-                    // only a box in global memory needs the fence (a fence here waits
-                    // for every outstanding store, e.g. the suppressed v above)
-                    if (nbox > kNmsRegBoxes * 64) wave_sync();
-                }
-            }
-        }
-    }
-}
-
-// PHASE 0: the whole of nms.Keypoints.annotations in one launch (suppression planes by
-// nms_plane_boxes); 1: up to the sorted keep list, whose count and occupancy-grid shape go
-// to the meta words (nms_planes_kernel runs the planes); 3: from the suppressed planes on.
-template <int W, int PHASE = 0>
-__global__ __launch_bounds__(64 * W) void nms_kernel(GrowArgs g) {
-    __shared__ ScoreLDS Ls[W];
-    __shared__ int s_m, s_m2, s_status;
-    __shared__ float s_mx, s_my;
-    const int img = blockIdx.x;
-    const int K = g.K;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    ScoreLDS &L = Ls[wave];
-    pp_ann *work = g.work + (int64_t)img * g.ann_cap;
-    pp_ann *out = g.out + (int64_t)img * g.ann_cap;
-    const int n_anns = max(0, min(g.n_work[img], g.ann_cap));
-    const int cap = g.ann_cap;
-    int *keep = g.nms_idx + (int64_t)img * (4 * cap + g.ann_np);  // kept work indices
-    int *surv = keep + cap;                                           // survivors
-    int *flag = surv + cap;                                           // per-index pass flags
-    int *perm2 = flag + cap;                                          // meta: m, grid h, w
-    int *perm = perm2 + cap;                                          // sort permutation
-    double *score = g.nms_score + (int64_t)img * 2 * cap;             // by work index
-    double *kscore = score + cap;                                     // by kept / survivor rank
-    float *amax = g.nms_f + (int64_t)img * 2 * cap;                   // per-ann max x, max y
-    int2 *gbox = g.nms_box + ((int64_t)img * kNmsBoxLists + wave) * cap;
-    const float red = (float)g.cfg.occupancy_reduction;
-    const float kt = g.cfg.nms_keypoint_threshold;
-    const double it = g.nms_it;
-    if (threadIdx.x == 0) {
-        s_status = g.status[img];
-        g.complete_next[img] = 0;  // workspace contract: left zero
-    }
-#ifdef PP_STAMPS
-    if (lane == 0)
-        for (int q = 0; q < 8; q++) L.fst[q] = 0;
-#endif
-    __syncthreads();
-    STAMP_DECL
-
-    if (PHASE == 0 && !g.cfg.apply_nms) {
-        for (int i = wave; i < n_anns; i += W) {
-            copy_ann(&out[i], &work[i]);
-            const double sc = nms_ann_score(g, L, img, i, work[i].data, K);
-            if (lane == 0) {
-                out[i].score = sc;
-                if (g.out_idx) g.out_idx[(int64_t)img * cap + i] = i;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            g.counts[img] = n_anns;
-            g.status[img] = s_status;
-        }
-        return;
-    }
-
-    int m = 0;
-    if constexpr (PHASE != 3) {
-    // nms.py:20-22: zero joints below keypoint_threshold, drop low scores (per annotation)
-    for (int i = wave; i < n_anns; i += W) {
-        pp_ann &a = work[i];
-        if (lane < K && a.data[lane][2] < kt) {
-            a.data[lane][0] = 0.0f;
-            a.data[lane][1] = 0.0f;
-            a.data[lane][2] = 0.0f;
-        }
-        wave_sync();
-        const double sc = nms_ann_score(g, L, img, i, a.data, K);
-        if (lane == 0) {
-            float ax = a.data[0][0], ay = a.data[0][1];
-            for (int j = 1; j < K; j++) {
-                ax = a.data[j][0] > ax ? a.data[j][0] : ax;
-                ay = a.data[j][1] > ay ? a.data[j][1] : ay;
-            }
-            score[i] = sc;
-            flag[i] = sc >= it;
-            amax[i] = ax;
-            amax[cap + i] = ay;
-        }
-    }
-    __syncthreads();
-    STAMP(2);
-    // keep list in work order + the occupancy shape (nms.py:27-31), then the stable sort
-    if (wave == 0) {
-        int m = 0;
-        float mx = 0.0f, my = 0.0f;
-        for (int i0 = 0; i0 < n_anns; i0 += 64) {
-            const int i = i0 + lane;
-            const bool k = i < n_anns && flag[i];
-            float ax = 0.0f, ay = 0.0f;
-            double sc = 0.0;
-            if (k) {
-                ax = amax[i];
-                ay = amax[cap + i];
-                sc = score[i];
-            }
-            const uint64_t km = __ballot(k);
-            if (k) {
-                const int r = m + lane_prefix(km);
-                keep[r] = i;
-                kscore[r] = sc;
-            }
-            uint64_t rest = km;
-            while (rest) {  // max over the kept annotations, in order (NaN behaviour)
-                const int l = __ffsll((unsigned long long)rest) - 1;
-                rest &= rest - 1;
-                const float lx = rl_f(ax, l), ly = rl_f(ay, l);
-                if (m == 0 || lx > mx) mx = lx;
-                if (m == 0 || ly > my) my = ly;
-                m++;
-            }
-        }
-        wave_sync();
-        if (m > 0) {
-            int np = 1;
-            while (np < m) np <<= 1;
-            sort_by_score(perm, np, m, kscore);  // nms.py:33 (stable)
-        }
-        if (lane == 0) {
-            s_m = m;
-            s_mx = mx;
-            s_my = my;
-        }
-    }
-    __syncthreads();
-    STAMP(3);
-    m = s_m;
+// The seed loop of a decode: seed_loop_ext_kernel when the images get external helper
+// workgroups (g.n_ext > 0), else seed_loop_kernel.
+int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s) {
+    // g.xext is zero: the workspace's zero region, which every external-helper seed
+    // loop leaves zero (ext_exit)
+    const size_t dyn = g.n_ext > 0 ? kExtDynLds : kColLds * sizeof(float);
+    // confidence_scales: their own kernel instances (the default ones carry no
+    // registers for them: complete_kernel stays at 128 VGPRs, 4 waves per SIMD)
+    const dim3 blk(64 * kSeedWaves);
+    if (g.n_ext > 0) {
+        const dim3 grid(n_img * (1 + g.n_ext));
+        if (g.has_cs)
+            hipLaunchKernelGGL(seed_loop_ext_kernel<true>, grid, blk, dyn, s, g);
+        else
+            hipLaunchKernelGGL(seed_loop_ext_kernel<false>, grid, blk, dyn, s, g);
+    } else if (g.has_cs) {
+        hipLaunchKernelGGL(seed_loop_kernel<true>, dim3(n_img), blk, dyn, s, g);
     } else {
-        m = perm2[0];
+        hipLaunchKernelGGL(seed_loop_kernel<false>, dim3(n_img), blk, dyn, s, g);
     }
-    if constexpr (PHASE == 1) {
-        if (threadIdx.x == 0) {
-            perm2[0] = m;
-            perm2[1] = perm2[2] = 0;
-            if (m > 0) {  // Occupancy((K, int(max y + 1), int(max x + 1)), 2, min_scale=4)
-                const long oh = (long)((double)(long)(s_my + 1.0f) / g.cfg.occupancy_reduction);
-                const long ow = (long)((double)(long)(s_mx + 1.0f) / g.cfg.occupancy_reduction);
-                perm2[1] = (int)(oh > 0 ? oh : 0);
-                perm2[2] = (int)(ow > 0 ? ow : 0);
-            }
-        }
-        return;
-    }
-    int n_out = 0;
-    if (m > 0) {
-        if constexpr (PHASE == 0) {
-        // Occupancy((K, int(max y + 1), int(max x + 1)), 2, min_scale=4)
-        const long oh = (long)((double)(long)(s_my + 1.0f) / g.cfg.occupancy_reduction);
-        const long ow = (long)((double)(long)(s_mx + 1.0f) / g.cfg.occupancy_reduction);
-        const OccGrid no = occ_grid(nullptr, K, (int)(oh > 0 ? oh : 0), (int)(ow > 0 ? ow : 0));
-        // the first 64 sorted annotations' joints of every plane this wave walks, loaded in
-        // one round trip (their work indices in one more) instead of three per plane
-        constexpr int kNmsPre = 4;  // planes per wave prefetched (K <= 32)
-        int wi0 = 0;
-        float pre[kNmsPre][4];
-        if (lane < m) wi0 = keep[perm[lane]];
-#pragma unroll
-        for (int u = 0; u < kNmsPre; u++) {
-            const int f = wave + u * W;
-            pre[u][0] = pre[u][1] = pre[u][2] = pre[u][3] = 0.0f;
-            if (f < K && lane < m) {
-                pre[u][0] = work[wi0].data[f][0];
-                pre[u][1] = work[wi0].data[f][1];
-                pre[u][2] = work[wi0].data[f][2];
-                pre[u][3] = work[wi0].joint_scales[f];
-            }
-        }
-        for (int f = wave, u = 0; f < K; f += W, u++) {  // nms.py:34-45, one plane per pass
-            nms_plane_boxes(g, work, m, f, no, red, gbox, [&](int r0, int &wi, float &jx, float &jy,
-                                                                float &jv, float &js) {
-                const int r = r0 + lane;
-                if (r0 == 0 && u < kNmsPre) {  // prefetched (selects: no dynamic index)
-                    wi = wi0;
-#pragma unroll
-                    for (int w = 0; w < kNmsPre; w++)
-                        if (w == u) {
-                            jx = pre[w][0];
-                            jy = pre[w][1];
-                            jv = pre[w][2];
-                            js = pre[w][3];
-                        }
-                } else if (r < m) {
-                    wi = keep[perm[r]];
-                    jx = work[wi].data[f][0];
-                    jy = work[wi].data[f][1];
-                    jv = work[wi].data[f][2];
-                    js = work[wi].joint_scales[f];
-                }
-            });
-        }
-        __syncthreads();
-        STAMP(4);
-        }
-        // nms.py:51-53 in sorted order: zero low joints, drop low scores
-        for (int r = wave; r < m; r += W) {
-            const int wi = keep[perm[r]];
-            pp_ann &a = work[wi];
-            if (lane < K && a.data[lane][2] < kt) {
-                a.data[lane][0] = 0.0f;
-                a.data[lane][1] = 0.0f;
-                a.data[lane][2] = 0.0f;
-            }
-            wave_sync();
-            const double sc = nms_ann_score(g, L, img, wi, a.data, K);
-            if (lane == 0) {
-                flag[r] = sc >= it;
-                score[r] = sc;  // by sorted rank now (the work-index scores are consumed)
-            }
-        }
-        __syncthreads();
-        STAMP(6);
-        if (wave == 0) {
-            int m2 = 0;
-            for (int r0 = 0; r0 < m; r0 += 64) {
-                const int r = r0 + lane;
-                const bool k = r < m && flag[r];
-                int wi = 0;
-                double sc = 0.0;
-                if (k) {
-                    wi = keep[perm[r]];
-                    sc = score[r];
-                }
-                const uint64_t km = __ballot(k);
-                if (k) {
-                    const int q = m2 + lane_prefix(km);
-                    surv[q] = wi;
-                    kscore[q] = sc;
-                }
-                m2 += __popcll(km);
-            }
-            wave_sync();
-            if (m2 > 0) {
-                int np2 = 1;
-                while (np2 < m2) np2 <<= 1;
-                sort_by_score(perm, np2, m2, kscore);  // nms.py:54
-            }
-            if (lane == 0) s_m2 = m2;
-        }
-        __syncthreads();
-        STAMP(7);
-        n_out = s_m2;
-        for (int r = wave; r < n_out; r += W) {
-            copy_ann(&out[r], &work[surv[perm[r]]]);
-            if (lane == 0) {
-                out[r].score = kscore[perm[r]];
-                if (g.out_idx) g.out_idx[(int64_t)img * cap + r] = surv[perm[r]];
-            }
-        }
-    }
-    __syncthreads();
-    STAMP(8);
-    if (wave == 0) {
-        STAMP_FLUSH(3);
-    }
-    if (threadIdx.x == 0) {
-        g.counts[img] = n_out;
-        g.status[img] = s_status;
-    }
+    return check_launch("pp_decode_batch(seed loop)");
 }
 
-}  // namespace pp
-
-namespace pp {
-
-// ---- nms.py:34-45 per (image, plane), the plane's occupancy as a bitmap in LDS ----
-// Between nms_kernel<W, 1> (the sorted keep list, its count and grid shape in the meta words)
-// and nms_kernel<W, 3> (the refilter and output): one wave per (image, joint plane), walking
-// the image's kept annotations in sorted order.  The reference's grid holds u8 counts and a
-// joint is occupied iff its cell's count is non-zero (mod 256: += 1 wraps).  Here a cell is
-// one bit, set when a marked box covers it: the same answer while no cell is covered by 256
-// boxes or more.  Counts of the boxes meeting each 32 x 32-cell block (never below any of
-// its cells' counts) guard that: a plane where a block reaches 256 boxes is decided again by
-// nms_plane_boxes (the exact counting form), which also takes grids larger than the LDS
-// bitmap (keypoints far outside the field).  Suppressed joints are written only after the
-// plane is decided.  A check is one LDS word, a mark one OR per (box row, word): O(m) per
-// plane instead of nms_plane_boxes' O(m * marked boxes / 64).
-constexpr int kNmsBlk = 32;
-
-struct NmsBitmapGeo {  // the LDS bitmap's capacity (the launch's dynamic LDS)
-    int cap_h, cap_w;  // grid rows and columns it holds
-    __host__ __device__ int wpr() const { return (cap_w + 31) >> 5; }
-    __host__ __device__ int blocks() const {
-        return ((cap_h + kNmsBlk - 1) / kNmsBlk) * ((cap_w + kNmsBlk - 1) / kNmsBlk);
-    }
-    __host__ __device__ size_t bytes(int ann_cap) const {
-        return sizeof(uint32_t) * ((size_t)cap_h * wpr() + blocks() + (ann_cap + 31) / 32);
-    }
-};
-
-__global__ __launch_bounds__(64) void nms_planes_kernel(GrowArgs g, NmsBitmapGeo geo) {
-    extern __shared__ uint32_t s_bm[];
-    const int img = blockIdx.x, f = blockIdx.y;
-    const int lane = threadIdx.x;
-    const int K = g.K, cap = g.ann_cap;
-    pp_ann *work = g.work + (int64_t)img * cap;
-    const int *keep = g.nms_idx + (int64_t)img * (4 * cap + g.ann_np);
-    const int *meta = keep + 3 * cap;  // nms_kernel<W, 1>: m, grid h, grid w
-    const int *perm = meta + cap;
-    const int m = meta[0], oh = meta[1], ow = meta[2];
-    if (m <= 0 || f >= K) return;
-    const float red = (float)g.cfg.occupancy_reduction;
-    const OccGrid no = occ_grid(nullptr, K, oh, ow);
-    auto load = [&](int r0, int &wi, float &jx, float &jy, float &jv, float &js) {
-        const int r = r0 + lane;
-        if (r < m) {
-            wi = keep[perm[r]];
-            jx = work[wi].data[f][0];
-            jy = work[wi].data[f][1];
-            jv = work[wi].data[f][2];
-            js = work[wi].joint_scales[f];
-        }
-    };
-    int2 *gbox = g.nms_box + ((int64_t)img * kNmsBoxLists + f) * cap;
-    if (oh <= 0 || ow <= 0 || oh > geo.cap_h || ow > geo.cap_w) {
-        nms_plane_boxes(g, work, m, f, no, red, gbox, load);
-        return;
-    }
-    const int wpr = (ow + 31) >> 5;
-    const int bcols = (ow + kNmsBlk - 1) / kNmsBlk;
-    uint32_t *bits = s_bm;                                // oh rows of wpr words
-    uint32_t *bcnt = s_bm + (size_t)geo.cap_h * geo.wpr();  // boxes per block
-    uint32_t *supp = bcnt + geo.blocks();                   // suppressed ranks
-    const int nbits = oh * wpr, nblk = ((oh + kNmsBlk - 1) / kNmsBlk) * bcols;
-    for (int i = lane; i < nbits; i += 64) bits[i] = 0u;
-    for (int i = lane; i < nblk; i += 64) bcnt[i] = 0u;
-    for (int i = lane; i < (m + 31) / 32; i += 64) supp[i] = 0u;
-    wave_sync();
-    bool over = false;
-    for (int r0 = 0; r0 < m; r0 += 64) {
-        int wi = 0;
-        float jx = 0.0f, jy = 0.0f, jv = 0.0f, js = 0.0f;
-        load(r0, wi, jx, jy, jv, js);
-        // per lane: its joint's cell, and the box it marks when free (0: none)
-        int xi = 0, yi = 0;
-        (void)occ_cell(no, f, jx, jy, red, xi, yi);  // -1: f < K and a non-empty grid
-        int box[4] = {0, 0, 0, 0};
-        const bool hb = r0 + lane < m && jv != 0.0f && occ_box(g, no, f, jx, jy, js, box);
-        const int cellp = xi | (yi << 16);
-        const int bxp = hb ? box[0] | (box[1] << 16) : 0;  // x1 >= 1 when hb: nonzero
-        const int byp = box[2] | (box[3] << 16);
-        const int nr = min(64, m - r0);
-        for (int l = 0; l < nr; l++) {
-            if (rl_f(jv, l) == 0.0f) continue;
-            const int cp = rl_i(cellp, l);
-            const int cx = cp & 0xFFFF, cy = cp >> 16;
-            if ((bits[cy * wpr + (cx >> 5)] >> (cx & 31)) & 1u) {  // occupied
-                if (lane == 0) atomicOr(&supp[(r0 + l) >> 5], 1u << ((r0 + l) & 31));
-                continue;
-            }
-            const int bx = rl_i(bxp, l);
-            if (bx == 0) continue;  // no box (empty after clipping)
-            const int by = rl_i(byp, l);
-            const int x0 = bx & 0xFFFF, x1 = bx >> 16, y0 = by & 0xFFFF, y1 = by >> 16;
-            const int w0 = x0 >> 5, nw = ((x1 - 1) >> 5) - w0 + 1;
-            const int items = (y1 - y0) * nw;
-            for (int t = lane; t < items; t += 64) {  // (box row, word) pairs
-                const int ry = y0 + t / nw, wq = w0 + t % nw;
-                const int lo = max(x0 - 32 * wq, 0), hi = min(x1 - 32 * wq, 32);
-                const uint32_t mk = (hi - lo >= 32) ? ~0u : (((1u << (hi - lo)) - 1u) << lo);
-                atomicOr(&bits[ry * wpr + wq], mk);
-            }
-            const int bx0 = x0 / kNmsBlk, bx1 = (x1 - 1) / kNmsBlk;
-            const int by0 = y0 / kNmsBlk, by1 = (y1 - 1) / kNmsBlk;
-            const int nbk = (bx1 - bx0 + 1) * (by1 - by0 + 1);
-            for (int t = lane; t < nbk; t += 64) {  // the guard: boxes per block
-                const int bq = (by0 + t / (bx1 - bx0 + 1)) * bcols + bx0 + t % (bx1 - bx0 + 1);
-                over |= atomicAdd(&bcnt[bq], 1u) >= 255u;
-            }
-            wave_sync();  // the marks before the next check
-        }
-    }
-    if (__ballot(over)) {  // a cell may have wrapped: decide the plane by counting
-        nms_plane_boxes(g, work, m, f, no, red, gbox, load);
-        return;
-    }
-    for (int r = lane; r < m; r += 64)  // nms.py:43: data[f, 2] *= suppression
-        if ((supp[r >> 5] >> (r & 31)) & 1u) {
-            float *v = &work[keep[perm[r]]].data[f][2];
-            *v = *v * g.cfg.nms_suppression;
-        }
-}
-
-}  // namespace pp
-
-// ---------------------------------------------------------------------------------------
-// host: workspace layout + pp_decode_batch
-// ---------------------------------------------------------------------------------------
-namespace pp {
-
-int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_config *cfg,
-                 pp_seed *seeds, int cap, int *counts, void *scratch, hipStream_t s,
-                 bool emitted);
-size_t seeds_scratch_size(int n_img, int cap);
-int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C,
-                        const int32_t *skeleton, const pp_config *cfg, float th, float *cols,
-                        int *offs, const int *gate, bool index_only, hipStream_t s);
-void caf_bucket_grid(int H, int W, int stride, int *bw, int *bh, int *nb, float *inv_e);
-
-static inline size_t align_up(size_t a) { return (a + 255) / 256 * 256; }
-
-struct DecodeLayout {
-    int hh, ww;
-    int64_t pitch, hw;
-    int seed_cap, ann_cap, ann_np, log_cap;
-    int bw, bh, nb;
-    float inv_e;
-    int64_t occ_cap;
-    size_t off_cifhr, off_hr_aux, off_hr_masks, off_cifhr_ws, off_seeds, off_seed_counts, off_seed_ws, off_cols[2],
-        off_offs[2], off_n_work, off_need, off_occ, off_wq, off_log, off_work, off_spec, off_xext, off_xrec, off_nms_score,
-        off_nms_idx, off_nms_f, off_nms_box, total;
-    size_t cifhr_ws_bytes;
-};
-
-// CifHr map from head 0 (cif_hr.py:46-51); column sets and seeds over the cells of all heads
-static DecodeLayout make_layout(int n_img, int K, int C, const Heads &h, const pp_config *cfg,
-                                int ann_cap) {
-    DecodeLayout d{};
-    d.hh = h.hr_hh;
-    d.ww = h.hr_ww;
-    d.pitch = pp_cifhr_pitch(d.ww);
-    d.hw = h.caf_cells();
-    d.seed_cap = (int)(K * h.cif_cells());  // every cell of every field: no seed overflow
-    d.ann_cap = ann_cap;
-    d.ann_np = 1;
-    while (d.ann_np < ann_cap) d.ann_np <<= 1;
-    d.log_cap = K * ann_cap;
-    const int64_t oh = (int64_t)((double)d.hh / cfg->occupancy_reduction);
-    const int64_t ow = (int64_t)((double)d.ww / cfg->occupancy_reduction);
-    d.occ_cap = (int64_t)align_up((size_t)(K * (oh + kOccMargin) * ((ow + kOccMargin + 15) & ~15)));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes);
-        return at;
-    };
-    const size_t n = (size_t)n_img;
-    // scratch CifHr, block-sparse (HrMap with masks): 64x64 tiles of 8x8 blocks
-    const HrMap geo = dense_hr(nullptr, d.hh, d.ww);
-    d.off_cifhr = take(n * K * (size_t)geo.tiles * kHrTile * kHrTile * sizeof(float));
-    d.off_hr_aux = take(h.n_groups > 1 ? n * K * (size_t)geo.tiles * kHrTile * kHrTile * sizeof(float) : 0);
-    d.off_hr_masks = take(n * K * (size_t)geo.tiles * sizeof(uint64_t));
-    d.cifhr_ws_bytes = std::max(cifhr_heads_workspace_size(h, n_img, K),
-                                cifhr_sparse_workspace_size(h, n_img, K));
-    d.off_cifhr_ws = take(d.cifhr_ws_bytes);
-    d.off_seeds = take(n * d.seed_cap * sizeof(pp_seed));
-    d.off_seed_counts = take(n * sizeof(int));
-    d.off_seed_ws = take(seeds_scratch_size(n_img, d.seed_cap));
-    caf_bucket_grid(h.cH[0], h.cW[0], h.cstride[0], &d.bw, &d.bh, &d.nb, &d.inv_e);
-    for (int t = 0; t < 2; t++) {
-        const bool used = t == 0 || cfg->force_complete;
-        d.off_cols[t] = take(used ? n * C * 2 * (t ? 1 : kColRows) * d.hw * sizeof(float) : 0);
-        d.off_offs[t] = take(used ? n * C * 2 * (d.nb + 1) * sizeof(int) : 0);
-    }
-    d.off_n_work = take(n * sizeof(int));
-    d.off_need = take(n * sizeof(int));
-    d.off_occ = take(n * d.occ_cap);  // zero region from here (pp_decode_workspace_zero_offset)
-    d.off_wq = take(n * sizeof(int));
-    d.off_log = take(n * d.log_cap * sizeof(OccLog));
-    d.off_work = take(n * ann_cap * sizeof(pp_ann));
-    d.off_spec = take(n * kSpecCache * sizeof(pp_ann));
-    d.off_xext = take(n * sizeof(SeedExt));
-    d.off_xrec = take(n * kExtCache * sizeof(pp_ann));
-    d.off_nms_score = take(n * 2 * ann_cap * sizeof(double));
-    d.off_nms_idx = take(n * (4 * ann_cap + d.ann_np) * sizeof(int));
-    d.off_nms_f = take(n * 2 * ann_cap * sizeof(float));
-    d.off_nms_box = take(n * kNmsBoxLists * ann_cap * sizeof(int2));
-    d.total = o;
-    return d;
+// force-complete, `ways` workgroups per image (they pull annotations from a per-image counter)
+int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s) {
+    const dim3 grid(n_img, ways);
+    if (g.has_cs)
+        hipLaunchKernelGGL(complete_kernel<true>, grid, dim3(64), 0, s, g);
+    else
+        hipLaunchKernelGGL(complete_kernel<false>, grid, dim3(64), 0, s, g);
+    return check_launch("pp_decode_batch(force complete)");
 }
 
 }  // namespace pp
 
 using namespace pp;
-
-extern "C" {
-
-size_t pp_decode_workspace_size(int32_t n_img, int32_t K, int32_t C, int32_t H, int32_t W,
-                                const pp_config *cfg, int32_t ann_capacity) {
-    if (!cfg || n_img < 0 || K <= 0 || C <= 0 || H <= 0 || W <= 0 || ann_capacity <= 0 ||
-        cfg->stride <= 0)
-        return 0;
-    return make_layout(n_img, K, C, single_head(nullptr, nullptr, H, W, cfg->stride), cfg,
-                       ann_capacity).total;
-}
-
-size_t pp_decode_workspace_zero_offset(int32_t n_img, int32_t K, int32_t C, int32_t H, int32_t W,
-                                       const pp_config *cfg, int32_t ann_capacity) {
-    if (!cfg || n_img <= 0 || K <= 0 || C <= 0 || H <= 0 || W <= 0 || ann_capacity <= 0 ||
-        cfg->stride <= 0)
-        return 0;
-    return make_layout(n_img, K, C, single_head(nullptr, nullptr, H, W, cfg->stride), cfg,
-                       ann_capacity).off_occ;
-}
-
-size_t pp_decode_work_offset(int32_t n_img, int32_t K, int32_t C, int32_t H, int32_t W,
-                             const pp_config *cfg, int32_t ann_capacity) {
-    if (!cfg || n_img <= 0 || K <= 0 || C <= 0 || H <= 0 || W <= 0 || ann_capacity <= 0 ||
-        cfg->stride <= 0)
-        return 0;
-    return make_layout(n_img, K, C, single_head(nullptr, nullptr, H, W, cfg->stride), cfg,
-                       ann_capacity).off_work;
-}
-
-size_t pp_decode_multi_work_offset(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,
-                                   int32_t n_img, int32_t K, int32_t C, const pp_config *cfg,
-                                   int32_t ann_capacity) {
-    Heads h;
-    if (!cfg || make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_multi_work_offset") ||
-        n_img <= 0 || K <= 0 || C <= 0 || ann_capacity <= 0)
-        return 0;
-    return make_layout(n_img, K, C, h, cfg, ann_capacity).off_work;
-}
-
-size_t pp_decode_multi_workspace_size(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,
-                                      int32_t n_img, int32_t K, int32_t C, const pp_config *cfg,
-                                      int32_t ann_capacity) {
-    Heads h;
-    if (!cfg || make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_multi_workspace_size") ||
-        n_img < 0 || K <= 0 || C <= 0 || ann_capacity <= 0)
-        return 0;
-    return make_layout(n_img, K, C, h, cfg, ann_capacity).total;
-}
-
-size_t pp_decode_multi_workspace_zero_offset(const pp_scale *scales, int32_t n_scales,
-                                             int32_t cif_pairs, int32_t n_img, int32_t K,
-                                             int32_t C, const pp_config *cfg,
-                                             int32_t ann_capacity) {
-    Heads h;
-    if (!cfg || make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_multi_workspace_zero_offset") ||
-        n_img <= 0 || K <= 0 || C <= 0 || ann_capacity <= 0)
-        return 0;
-    return make_layout(n_img, K, C, h, cfg, ann_capacity).off_occ;
-}
-
-}  // extern "C"
-
-namespace pp {
-
-// One non-blocking side stream (+ fork / join events) per device, created on first use;
-// the mutex keeps concurrent host threads' fork / join pairs from interleaving.
-struct SideStream {
-    hipStream_t stream;
-    hipEvent_t fork, join;
-    mutable std::mutex mu;
-};
-
-static const SideStream *side_stream() {
-    static std::mutex create_mu;
-    static SideStream *per_dev[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(create_mu);
-    if (!per_dev[dev]) {
-        SideStream *ss = new SideStream();
-        if (hipStreamCreateWithFlags(&ss->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ss->fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ss->join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            delete ss;
-            return nullptr;
-        }
-        per_dev[dev] = ss;
-    }
-    return per_dev[dev];
-}
-
-// External helper workgroups per image for the seed loop: enough to give every CU a seed
-// loop workgroup when the batch has fewer images than CUs (at most kExtWgMax).
-static int seed_ext_per_image(int n_img) {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cus[dev] <= 0 &&
-        hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-        (void)hipGetLastError();
-        cus[dev] = 0;
-    }
-    if (n_img <= 0 || cus[dev] <= 0) return 0;
-    return std::max(0, std::min(kExtWgMax, cus[dev] / n_img - 1));
-}
-
-// Force-complete workgroups per image.  The workgroups pull annotations from a per-image
-// counter, so any count gives the same result; 8 or 16 for sparse batches measured no
-// better than 64 (round 5).
-static int complete_ways(uint32_t) { return kCompleteWays; }
-
-// nms.Keypoints (nms.py:17-57) of a decode: nms_kernel<W> in one launch, or with `bitmap`
-// (PP_STAGE_NMS_BITMAP) nms_kernel<W, 1>, the planes as
-// bitmaps (nms_planes_kernel, one wave per (image, plane)), nms_kernel<W, 3> -- unless NMS
-// is off or the bitmap would not fit kNmsBitmapLds.  `wide`: 8-wave workgroups
-// (PP_STAGE_NMS_WIDE).  The bitmap holds the nominal grid (CifHr map / reduction) plus
-// kNmsMargin cells; an image whose keypoints reach further takes nms_plane_boxes in the
-// plane kernel.  Measured (round 5, one box): the three launches take 60 vs 76 us per planted
-// cfg3 step and 1.48 vs 2.51 ms per uniform one, one step at a time; but in the overlapped
-// pipeline planted 397k-402k vs 405k-410k and uniform 14.7k vs 15.5k-15.8k images/s (the
-// 4352 one-wave workgroups of the plane kernel beside the next batch's seed loop), so the
-// single launch stays the default.
-constexpr int kNmsMargin = 16;
-constexpr size_t kNmsBitmapLds = 64 * 1024;
-
-static int launch_nms(const GrowArgs &g, int n_img, bool wide, bool bitmap, hipStream_t s) {
-    NmsBitmapGeo geo{};
-    geo.cap_h = (int)((double)g.hh / g.cfg.occupancy_reduction) + kNmsMargin;
-    geo.cap_w = (int)((double)g.ww / g.cfg.occupancy_reduction) + kNmsMargin;
-    const size_t lds = geo.bytes(g.ann_cap);
-    if (bitmap && g.cfg.apply_nms && lds <= kNmsBitmapLds) {
-        if (wide)
-            hipLaunchKernelGGL((nms_kernel<kNmsWaves, 1>), dim3(n_img), dim3(64 * kNmsWaves), 0, s, g);
-        else
-            hipLaunchKernelGGL((nms_kernel<kNmsNarrow, 1>), dim3(n_img), dim3(64 * kNmsNarrow), 0, s, g);
-        hipLaunchKernelGGL(nms_planes_kernel, dim3(n_img, g.K), dim3(64), lds, s, g, geo);
-        if (wide)
-            hipLaunchKernelGGL((nms_kernel<kNmsWaves, 3>), dim3(n_img), dim3(64 * kNmsWaves), 0, s, g);
-        else
-            hipLaunchKernelGGL((nms_kernel<kNmsNarrow, 3>), dim3(n_img), dim3(64 * kNmsNarrow), 0, s, g);
-        return check_launch("pp_decode_batch(nms)");
-    }
-    if (wide)
-        hipLaunchKernelGGL(nms_kernel<kNmsWaves>, dim3(n_img), dim3(64 * kNmsWaves), 0, s, g);
-    else
-        hipLaunchKernelGGL(nms_kernel<kNmsNarrow>, dim3(n_img), dim3(64 * kNmsNarrow), 0, s, g);
-    return check_launch("pp_decode_batch(nms)");
-}
-
-// optional inputs of pp_decode_initial
-struct DecodeInit {
-    const pp_ann *anns = nullptr;
-    const int32_t *counts = nullptr;
-    int32_t cap = 0;
-    int32_t *out_index = nullptr;
-};
-
-static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
-                        const int32_t *skeleton, const pp_config *cfg, float *d_cifhr,
-                        pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                        int32_t *d_status, void *d_workspace, size_t workspace_bytes,
-                        uint32_t stages, void *stream, const DecodeInit &init = DecodeInit{}) {
-    if (!skeleton || !cfg || !d_anns || !d_counts || !d_status || !d_workspace)
-        return fail(PP_EINVAL, "pp_decode_batch: NULL argument");
-    for (int m = 0; m < h.n_cif; m++)
-        if (!h.cif[m]) return fail(PP_EINVAL, "pp_decode_batch: NULL CIF field");
-    for (int m = 0; m < h.n_caf; m++)
-        if (!h.caf[m]) return fail(PP_EINVAL, "pp_decode_batch: NULL CAF field");
-    if (n_img < 0 || K <= 0 || K > PP_MAX_KP || C <= 0 || C > PP_MAX_EDGES ||
-        ann_capacity <= 0 || cfg->occupancy_reduction <= 0)
-        return fail(PP_ESHAPE, "pp_decode_batch: shape outside the supported envelope "
-                               "(K <= PP_MAX_KP, C <= PP_MAX_EDGES)");
-    if (cfg->connection_method != 0 && cfg->connection_method != 1)
-        return fail(PP_EINVAL, "connection method not known");
-    for (int i = 0; i < 2 * C; i++)
-        if (skeleton[i] < 1 || skeleton[i] > K)
-            return fail(PP_EINVAL, "pp_decode_batch: skeleton joint index out of 1..K");
-    if ((int64_t)K * h.cif_cells() > INT32_MAX || h.caf_cells() > INT32_MAX)
-        return fail(PP_ESHAPE, "pp_decode_batch: fields too large");
-    if (n_img == 0) return PP_OK;
-    const DecodeLayout d = make_layout(n_img, K, C, h, cfg, ann_capacity);
-    if (workspace_bytes < d.total) return fail(PP_ENOMEM, "pp_decode_batch: workspace too small");
-    if ((int64_t)d.hh >= kMaxHrSide || (int64_t)d.ww >= kMaxHrSide)
-        return fail(PP_ESHAPE, "pp_decode_batch: field too large (CifHr map of 32768 px or "
-                               "more per side)");
-    char *ws = (char *)d_workspace;
-    hipStream_t s = (hipStream_t)stream;
-    // the caller's d_cifhr gets the dense map; otherwise the decoder keeps the block-sparse
-    // scratch map, written only where splat boxes land
-    float *hr_base = d_cifhr ? d_cifhr : (float *)(ws + d.off_cifhr);
-    uint64_t *hr_masks = d_cifhr ? nullptr : (uint64_t *)(ws + d.off_hr_masks);
-    HrMap hr = dense_hr(hr_base, d.hh, d.ww);
-    hr.masks = hr_masks;
-    pp_seed *seeds = (pp_seed *)(ws + d.off_seeds);
-    int *seed_counts = (int *)(ws + d.off_seed_counts);
-    float *cols[2] = {(float *)(ws + d.off_cols[0]), (float *)(ws + d.off_cols[1])};
-    int *offs[2] = {(int *)(ws + d.off_offs[0]), (int *)(ws + d.off_offs[1])};
-    int rc = PP_OK;
-    // PP_STAGE_COMPLETE_SETS_EARLY with stage 1 (and without 8): the force-complete sets read
-    // only the CAF fields, so they start on the side stream before the CifHr map, and a later
-    // call's side-stream join (stages 2 | 4) covers them
-    const bool b_first = (stages & PP_STAGE_COMPLETE_SETS_EARLY) && (stages & 1u) &&
-                         !(stages & 8u) && cfg->force_complete;
-    if (b_first) {
-        const SideStream *side = side_stream();
-        if (!side) return fail(PP_EHIP, "pp_decode_stages: no side stream for stage 16");
-        std::lock_guard<std::mutex> lock(side->mu);
-        if (hipEventRecord(side->fork, s) != hipSuccess ||
-            hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
-        rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                 cols[1], offs[1], nullptr, true, side->stream);
-        if (rc) {
-            (void)hipEventRecord(side->join, side->stream);
-            (void)hipStreamWaitEvent(s, side->join, 0);
-            return rc;
-        }
-    }
-    // the block-sparse map's kernel emits the seeds too when it can (stage 1 then writes
-    // what seeds_emit_kernel would; stage 2 sorts them): the same test in both stages
-    const bool fused_seeds = !d_cifhr && cifhr_fuses_seeds(h, n_img, K, cfg);
-    if (stages & 1u) {
-        if (d_cifhr) {
-            rc = cifhr_heads_launch<false>(h, n_img, K, cfg, d_cifhr, ws + d.off_cifhr_ws,
-                                           d.cifhr_ws_bytes, s, "pp_decode_batch(cifhr)");
-        } else {
-            const SeedSink sink = seed_sink(n_img, K, cfg, d.seed_cap, ws + d.off_seed_ws);
-            rc = cifhr_sparse_launch(h, n_img, K, cfg, hr_base, (float *)(ws + d.off_hr_aux),
-                                     hr_masks, ws + d.off_cifhr_ws, d.cifhr_ws_bytes, s,
-                                     "pp_decode_batch(cifhr)", fused_seeds ? &sink : nullptr);
-        }
-        if (rc) return rc;
-    }
-    // CifSeeds and CafScored both read only the fields and the CifHr map: with both stages
-    // requested, CafScored runs on a side stream beside the seeds (fork / join events)
-    // PP_STAGE_COMPLETE_SETS_EARLY: the force-complete sets (every field and direction) with
-    // CafScored instead of gated after the seed loop
-    const bool early_b = (stages & PP_STAGE_COMPLETE_SETS_EARLY) && (stages & 4u) &&
-                         !(stages & 1u) && cfg->force_complete;
-    const SideStream *side = (stages & 6u) == 6u ? side_stream() : nullptr;
-    if (side) {
-        std::lock_guard<std::mutex> lock(side->mu);
-        if (hipEventRecord(side->fork, s) != hipSuccess ||
-            hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
-        rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold, cols[0],
-                                 offs[0], nullptr, false, side->stream);
-        if (!rc && early_b)
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
-                                     cfg->complete_caf_threshold, cols[1], offs[1], nullptr, true,
-                                     side->stream);
-        if (!rc)
-            rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds);
-        // join even after a failed launch, so the caller's stream never runs ahead
-        if (hipEventRecord(side->join, side->stream) != hipSuccess ||
-            hipStreamWaitEvent(s, side->join, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream join failed");
-        if (rc) return rc;
-    } else {
-        if (stages & 2u) {
-            rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds);
-            if (rc) return rc;
-        }
-        if (stages & 4u) {  // CafScored at caf_threshold; the force-complete set is lazy
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold,
-                                     cols[0], offs[0], nullptr, false, s);
-            if (!rc && early_b)
-                rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
-                                         cfg->complete_caf_threshold, cols[1], offs[1], nullptr,
-                                         true, s);
-            if (rc) return rc;
-        }
-    }
-    if (stages & 8u) {
-        GrowArgs g{};
-        g.seeds = seeds;
-        g.seed_counts = seed_counts;
-        g.seed_cap = d.seed_cap;
-        g.cols[0] = cols[0];
-        g.cols[1] = cols[1];
-        g.offs[0] = offs[0];
-        g.offs[1] = offs[1];
-        g.bw = d.bw;
-        g.bh = d.bh;
-        g.nb = d.nb;
-        g.inv_e = d.inv_e;
-        g.K = K;
-        g.C = C;
-        g.hh = d.hh;
-        g.ww = d.ww;
-        g.col_cap = d.hw;
-        g.cfg = *cfg;
-        g.nms_it = (double)cfg->nms_instance_threshold;
-        g.heads = h;
-        g.hr = hr;
-        g.cif_floor = cfg->cif_floor;
-        g.one_minus_floor = (float)(1.0 - (double)cfg->cif_floor);  // (1.0 - self.cif_floor)
-        g.th_b = cfg->complete_caf_threshold;
-        for (int ci = 0; ci < C; ci++) {
-            g.caf_j1[ci] = (uint8_t)(skeleton[2 * ci] - 1);
-            g.caf_j2[ci] = (uint8_t)(skeleton[2 * ci + 1] - 1);
-        }
-        // by_source (cifcaf.py:62-65): dict insertion order, later duplicate keys
-        // overwrite the value in place; flattened into directed-edge slots per start joint
-        {
-            int nbs[kKP] = {0};
-            int bk[kKP][kKP], bc[kKP][kKP], bf[kKP][kKP];
-            for (int ci = 0; ci < C; ci++) {
-                const int j1 = skeleton[2 * ci] - 1, j2 = skeleton[2 * ci + 1] - 1;
-                const int ins[2][3] = {{j1, j2, 1}, {j2, j1, 0}};
-                for (int t = 0; t < 2; t++) {
-                    const int st = ins[t][0];
-                    int pos = -1;
-                    for (int e = 0; e < nbs[st]; e++)
-                        if (bk[st][e] == ins[t][1]) pos = e;
-                    if (pos < 0) pos = nbs[st]++;
-                    bk[st][pos] = ins[t][1];
-                    bc[st][pos] = ci;
-                    bf[st][pos] = ins[t][2];
-                }
-            }
-            int d = 0;
-            for (int j = 0; j < K; j++) {
-                g.j_off[j] = (uint8_t)d;
-                for (int e = 0; e < nbs[j]; e++, d++) {
-                    g.d_j[d] = (uint8_t)j;
-                    g.d_k[d] = (uint8_t)bk[j][e];
-                    g.d_caf[d] = (uint8_t)bc[j][e];
-                    g.d_fwd[d] = (uint8_t)bf[j][e];
-                }
-            }
-            g.j_off[K] = (uint8_t)d;
-            g.nd = d;
-            g.has_cs = cfg->confidence_scales != nullptr;
-            for (int e = 0; e < kSlots; e++)
-                g.slot_cs[e] = (g.has_cs && e < d) ? cfg->confidence_scales[g.d_caf[e]] : 1.0f;
-        }
-        g.occ = (uint8_t *)(ws + d.off_occ);
-        g.occ_cap = d.occ_cap;
-        g.log = (OccLog *)(ws + d.off_log);
-        g.log_cap = d.log_cap;
-        g.work = (pp_ann *)(ws + d.off_work);
-        g.spec = (pp_ann *)(ws + d.off_spec);
-        g.spec_far = kSpecFar;
-        g.n_ext = seed_ext_per_image(n_img);
-        g.xext = (SeedExt *)(ws + d.off_xext);
-        g.xrec = (pp_ann *)(ws + d.off_xrec);
-        g.nms_score = (double *)(ws + d.off_nms_score);
-        g.nms_idx = (int *)(ws + d.off_nms_idx);
-        g.nms_f = (float *)(ws + d.off_nms_f);
-        g.nms_box = (int2 *)(ws + d.off_nms_box);
-        g.ann_np = d.ann_np;
-        g.ann_cap = ann_capacity;
-        g.stamps = nullptr;
-#ifdef PP_STAMPS
-        hipMalloc((void **)&g.stamps, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t));
-        hipMemsetAsync(g.stamps, 0, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t), s);
-        uint64_t *gcs = nullptr;
-        hipMalloc((void **)&gcs, (size_t)n_img * 4 * sizeof(uint64_t));
-        hipMemsetAsync(gcs, 0, (size_t)n_img * 4 * sizeof(uint64_t), s);
-        hipMemcpyToSymbolAsync(HIP_SYMBOL(g_gc_stamps), &gcs, sizeof(gcs), 0,
-                               hipMemcpyHostToDevice, s);
-#endif
-        g.n_work = (int *)(ws + d.off_n_work);
-        g.need_complete = (int *)(ws + d.off_need);
-        g.complete_next = (int *)(ws + d.off_wq);
-        g.init = init.anns;
-        g.init_counts = init.counts;
-        g.init_cap = init.cap;
-        g.out_idx = init.out_index;
-        g.out = d_anns;
-        g.counts = d_counts;
-        g.status = d_status;
-        // PP_STAGE_SEED_LOOP_ONLY / PP_STAGE_AFTER_SEED_LOOP split stage 8 in two calls
-        const bool run_rest = !(stages & PP_STAGE_SEED_LOOP_ONLY);
-        if (!(stages & PP_STAGE_AFTER_SEED_LOOP)) {
-            // g.xext is zero: the workspace's zero region, which every external-helper seed
-            // loop leaves zero (ext_exit)
-            const size_t dyn = g.n_ext > 0 ? kExtDynLds : kColLds * sizeof(float);
-            // confidence_scales: their own kernel instances (the default ones carry no
-            // registers for them: complete_kernel stays at 128 VGPRs, 4 waves per SIMD)
-            const dim3 blk(64 * kSeedWaves);
-            if (g.n_ext > 0) {
-                const dim3 grid(n_img * (1 + g.n_ext));
-                if (g.has_cs)
-                    hipLaunchKernelGGL(seed_loop_ext_kernel<true>, grid, blk, dyn, s, g);
-                else
-                    hipLaunchKernelGGL(seed_loop_ext_kernel<false>, grid, blk, dyn, s, g);
-            } else if (g.has_cs) {
-                hipLaunchKernelGGL(seed_loop_kernel<true>, dim3(n_img), blk, dyn, s, g);
-            } else {
-                hipLaunchKernelGGL(seed_loop_kernel<false>, dim3(n_img), blk, dyn, s, g);
-            }
-            rc = check_launch("pp_decode_batch(seed loop)");
-            if (rc) return rc;
-        }
-        // PP_STAGE_COMPLETE_ONLY / PP_STAGE_NMS_ONLY split the rest once more
-        const bool run_complete = run_rest && !(stages & PP_STAGE_NMS_ONLY);
-        const bool run_nms = run_rest && !(stages & PP_STAGE_COMPLETE_ONLY);
-        if (run_complete && cfg->force_complete && !(stages & PP_STAGE_COMPLETE_SETS_EARLY)) {
-            // complete_annotations' CafScored(score_th=0.0001) only where phase 1 left work
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                     cols[1], offs[1], g.need_complete, true, s);
-            if (rc) return rc;
-        }
-        if (run_complete && cfg->force_complete) {
-            const dim3 grid(n_img, complete_ways(stages));
-            if (g.has_cs)
-                hipLaunchKernelGGL(complete_kernel<true>, grid, dim3(64), 0, s, g);
-            else
-                hipLaunchKernelGGL(complete_kernel<false>, grid, dim3(64), 0, s, g);
-            rc = check_launch("pp_decode_batch(force complete)");
-            if (rc) return rc;
-        }
-        if (run_nms)
-            rc = launch_nms(g, n_img, (stages & PP_STAGE_NMS_WIDE) && g.n_ext == 0,
-                            (stages & PP_STAGE_NMS_BITMAP) != 0, s);
-#ifdef PP_STAMPS
-        hipStreamSynchronize(s);
-        const size_t nst = (size_t)n_img * 3 * kStampSlots;
-        uint64_t *h = (uint64_t *)malloc(nst * sizeof(uint64_t));
-        hipMemcpy(h, g.stamps, nst * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        const char *path = getenv("PP_STAMPS_OUT");
-        FILE *fo = fopen(path ? path : "pp_stamps.bin", "ab");
-        if (fo) {
-            fwrite(h, sizeof(uint64_t), nst, fo);
-            fclose(fo);
-        }
-        free(h);
-        hipFree(g.stamps);
-        uint64_t *hg = (uint64_t *)malloc((size_t)n_img * 4 * sizeof(uint64_t));
-        hipMemcpy(hg, gcs, (size_t)n_img * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int i = 0; i < n_img; i++) {
-            a0 += hg[4 * i];
-            a1 += hg[4 * i + 1];
-            a2 += hg[4 * i + 2];
-        }
-        fprintf(stderr, "grow_connection sections per image: offsets+scan-setup %.0f  columns %.0f  merge %.0f\n",
-                a0 / n_img, a1 / n_img, a2 / n_img);
-        free(hg);
-        hipFree(gcs);
-#endif
-    }
-    return rc;
-}
-
-}  // namespace pp
-
-extern "C" {
-
-int pp_decode_stages(const float *d_cif, const float *d_caf, int32_t n_img, int32_t K, int32_t C,
-                     int32_t H, int32_t W, const int32_t *skeleton, const pp_config *cfg,
-                     float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                     int32_t *d_status, void *d_workspace, size_t workspace_bytes,
-                     uint32_t stages, void *stream) {
-    if (!d_cif || !d_caf || !cfg) return fail(PP_EINVAL, "pp_decode_batch: NULL argument");
-    if (H <= 0 || W <= 0 || cfg->stride <= 0) return fail(PP_ESHAPE, "pp_decode_batch: bad shape");
-    return decode_heads(single_head(d_cif, d_caf, H, W, cfg->stride), n_img, K, C, skeleton, cfg,
-                        d_cifhr, d_anns, ann_capacity, d_counts, d_status, d_workspace,
-                        workspace_bytes, stages, stream);
-}
-
-int pp_decode_multi(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs, int32_t n_img,
-                    int32_t K, int32_t C, const int32_t *skeleton, const pp_config *cfg,
-                    float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                    int32_t *d_status, void *d_workspace, size_t workspace_bytes,
-                    uint32_t stages, void *stream) {
-    Heads h;
-    const int rc = make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_multi");
-    if (rc) return rc;
-    return decode_heads(h, n_img, K, C, skeleton, cfg, d_cifhr, d_anns, ann_capacity, d_counts,
-                        d_status, d_workspace, workspace_bytes, stages, stream);
-}
-
-int pp_decode_initial(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs, int32_t n_img,
-                      int32_t K, int32_t C, const int32_t *skeleton, const pp_config *cfg,
-                      float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                      int32_t *d_status, const pp_ann *d_initial, const int32_t *d_initial_counts,
-                      int32_t initial_capacity, int32_t *d_out_index, void *d_workspace,
-                      size_t workspace_bytes, uint32_t stages, void *stream) {
-    Heads h;
-    const int rc = make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_initial");
-    if (rc) return rc;
-    if ((d_initial == nullptr) != (d_initial_counts == nullptr))
-        return fail(PP_EINVAL, "pp_decode_initial: d_initial and d_initial_counts go together");
-    if (d_initial && initial_capacity <= 0)
-        return fail(PP_ESHAPE, "pp_decode_initial: bad initial_capacity");
-    DecodeInit init;
-    init.anns = d_initial;
-    init.counts = d_initial_counts;
-    init.cap = d_initial ? initial_capacity : 0;
-    init.out_index = d_out_index;
-    return decode_heads(h, n_img, K, C, skeleton, cfg, d_cifhr, d_anns, ann_capacity, d_counts,
-                        d_status, d_workspace, workspace_bytes, stages, stream, init);
-}
-
-// ---- standalone nms.Keypoints.annotations (nms.py:17-57) over caller records ----------
-namespace {
-struct NmsLayout {
-    size_t off_status, off_wq, off_score, off_idx, off_f, off_box, total;
-    int ann_np;
-};
-NmsLayout nms_layout(int n_img, int cap) {
-    NmsLayout l{};
-    l.ann_np = 1;
-    while (l.ann_np < cap) l.ann_np <<= 1;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align_up(bytes);
-        return at;
-    };
-    const size_t n = (size_t)n_img;
-    l.off_status = take(n * sizeof(int));
-    l.off_wq = take(n * sizeof(int));
-    l.off_score = take(n * 2 * cap * sizeof(double));
-    l.off_idx = take(n * (4 * (size_t)cap + l.ann_np) * sizeof(int));
-    l.off_f = take(n * 2 * cap * sizeof(float));
-    l.off_box = take(n * kNmsWaves * (size_t)cap * sizeof(int2));
-    l.total = o;
-    return l;
-}
-}  // namespace
-
-size_t pp_nms_workspace_size(int32_t n_img, int32_t ann_capacity) {
-    if (n_img < 0 || ann_capacity <= 0) return 0;
-    return nms_layout(n_img, ann_capacity).total;
-}
-
-int pp_nms_keypoints(pp_ann *d_anns, const int32_t *d_counts, int32_t n_img, int32_t K,
-                     int32_t ann_capacity, const pp_config *cfg, pp_ann *d_out,
-                     int32_t *d_out_counts, int32_t *d_out_index, void *d_workspace,
-                     size_t workspace_bytes, void *stream) {
-    if (!cfg) return fail(PP_EINVAL, "pp_nms_keypoints: NULL argument");
-    return pp_nms_keypoints_scored(d_anns, d_counts, n_img, K, ann_capacity, cfg,
-                                   (double)cfg->nms_instance_threshold, nullptr, nullptr,
-                                   nullptr, d_out, d_out_counts, d_out_index, d_workspace,
-                                   workspace_bytes, stream);
-}
-
-int pp_nms_keypoints_scored(pp_ann *d_anns, const int32_t *d_counts, int32_t n_img, int32_t K,
-                            int32_t ann_capacity, const pp_config *cfg,
-                            double instance_threshold, const int32_t *d_score_spec, const double *d_score_weights,
-                            const double *d_fixed_score, pp_ann *d_out, int32_t *d_out_counts,
-                            int32_t *d_out_index, void *d_workspace, size_t workspace_bytes,
-                            void *stream) {
-    if (!d_anns || !d_counts || !cfg || !d_out || !d_out_counts || !d_workspace)
-        return fail(PP_EINVAL, "pp_nms_keypoints: NULL argument");
-    if (d_score_spec && (!d_score_weights || !d_fixed_score))
-        return fail(PP_EINVAL, "pp_nms_keypoints_scored: d_score_spec needs the weights and "
-                               "fixed scores");
-    if (n_img < 0 || K <= 0 || K > PP_MAX_KP || ann_capacity <= 0 || cfg->occupancy_reduction <= 0)
-        return fail(PP_ESHAPE, "pp_nms_keypoints: shape outside the supported envelope");
-    if (n_img == 0) return PP_OK;
-    const NmsLayout l = nms_layout(n_img, ann_capacity);
-    if (workspace_bytes < l.total) return fail(PP_ENOMEM, "pp_nms_keypoints: workspace too small");
-    char *ws = (char *)d_workspace;
-    hipStream_t s = (hipStream_t)stream;
-    GrowArgs g{};
-    g.K = K;
-    g.cfg = *cfg;
-    g.cfg.apply_nms = 1;
-    g.work = d_anns;
-    g.n_work = const_cast<int *>(d_counts);
-    g.ann_cap = ann_capacity;
-    g.ann_np = l.ann_np;
-    g.status = (int *)(ws + l.off_status);
-    g.complete_next = (int *)(ws + l.off_wq);
-    g.nms_score = (double *)(ws + l.off_score);
-    g.nms_idx = (int *)(ws + l.off_idx);
-    g.nms_f = (float *)(ws + l.off_f);
-    g.nms_box = (int2 *)(ws + l.off_box);
-    g.nms_spec = d_score_spec;
-    g.nms_sw = d_score_weights;
-    g.nms_fixed = d_fixed_score;
-    g.nms_it = instance_threshold;
-    g.out = d_out;
-    g.counts = d_out_counts;
-    g.out_idx = d_out_index;
-    if (hipMemsetAsync(g.status, 0, (size_t)n_img * sizeof(int), s) != hipSuccess)
-        return fail(PP_EHIP, "pp_nms_keypoints: memset failed");
-    hipLaunchKernelGGL(nms_kernel<kNmsWaves>, dim3(n_img), dim3(64 * kNmsWaves), 0, s, g);
-    return check_launch("pp_nms_keypoints");
-}
-
-int pp_decode_batch(const float *d_cif, const float *d_caf, int32_t n_img, int32_t K, int32_t C,
-                    int32_t H, int32_t W, const int32_t *skeleton, const pp_config *cfg,
-                    float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                    int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
-    return pp_decode_stages(d_cif, d_caf, n_img, K, C, H, W, skeleton, cfg, d_cifhr, d_anns,
-                            ann_capacity, d_counts, d_status, d_workspace, workspace_bytes, 15u,
-                            stream);
-}
-
-}  // extern "C"
 
 // ---------------------------------------------------------------------------------------
 // one _grow_connection (+ blend / max) on a device column set, for the functional API
@@ -4245,4 +2597,3 @@ extern "C" int pp_grow_connection(const float *d_cols, int64_t n, int64_t pitch,
                            pitch, x, y, xy_scale, exp_mode, d_out);
     return check_launch("pp_grow_connection");
 }
-

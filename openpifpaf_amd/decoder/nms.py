@@ -1,7 +1,7 @@
 """Keypoint and detection NMS (nms.py:11-102).
 
 Inside the device decode the suppression runs after the seed loop and force-complete
-(csrc/grow.hip, nms_kernel), configured from these class attributes exactly as the
+(csrc/nms.hip, nms_kernel), configured from these class attributes exactly as the
 reference's CifCaf(nms=nms.Keypoints()) is.  `Keypoints().annotations(anns)` runs the
 same kernel over a host list of Annotation objects (pp_nms_keypoints): it mutates their
 data in place as the reference does and returns the survivors, sorted by -score.  Each

@@ -156,6 +156,64 @@ def test_scale_struct_and_multi_workspace():
     assert lib.pp_cifhr_multi_workspace_size(cif_only, 1, 0, 1, 17) > 0
 
 
+def _workspace_grid(lib):
+    """(workspace size, zero offset, work offset) of the single-scale and of the multi-scale
+    sizing entry points over a grid of shapes, K = 17, C = 19."""
+    import ctypes
+    from openpifpaf_amd._abi import make_config, scale_list
+    arr = scale_list([(0, 41, 41), (0, 21, 21)], [(0, 41, 41), (0, 21, 21)], [8, 16], [8, 16],
+                     [0.0, 12.0], [0.0, 36.0], [160.0, None])
+    single, multi = [], []
+    for fc in (True, False):
+        cfg = ctypes.byref(make_config(force_complete=fc))
+        for n_img in (0, 1, 2, 256):
+            for cap in (128, 800):
+                for hw in (41, 80):
+                    single.append((lib.pp_decode_workspace_size(n_img, 17, 19, hw, hw, cfg, cap),
+                                   lib.pp_decode_workspace_zero_offset(n_img, 17, 19, hw, hw, cfg, cap),
+                                   lib.pp_decode_work_offset(n_img, 17, 19, hw, hw, cfg, cap)))
+                multi.append((lib.pp_decode_multi_workspace_size(arr, 4, 0, n_img, 17, 19, cfg, cap),
+                              lib.pp_decode_multi_workspace_zero_offset(arr, 4, 0, n_img, 17, 19, cfg, cap),
+                              lib.pp_decode_multi_work_offset(arr, 4, 0, n_img, 17, 19, cfg, cap)))
+    return single, multi
+
+
+def test_workspace_layout_pinned(lib):
+    """The six workspace size / offset entry points return what they returned before they were
+    folded onto one helper (recorded from that build): force_complete on then off, n_img 0, 1,
+    2, 256, ann_capacity 128, 800, fields 41x41 and 80x80 (single) or the 4-head pp_scale
+    array of test_scale_struct_and_multi_workspace (multi)."""
+    single, multi = _workspace_grid(lib)
+    assert single == WORKSPACE_SINGLE
+    assert multi == WORKSPACE_MULTI
+
+
+WORKSPACE_SINGLE = [
+    (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0),
+    (218801920, 217619968, 218499328), (633435648, 630626048, 633133056),
+    (220136192, 217619968, 218636544), (634769920, 630626048, 633270272),
+    (233600768, 231237632, 232996096), (677782272, 672163840, 677177600),
+    (236269056, 231237632, 233270272), (680450560, 672163840, 677451776),
+    (4660591616, 4358154240, 4583205888), (13867951104, 13148835840, 13790565376),
+    (5002132480, 4358154240, 4618300416), (14209491968, 13148835840, 13825659904),
+    (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0),
+    (218478592, 217296640, 218176000), (632219136, 629409536, 631916544),
+    (219812864, 217296640, 218313216), (633553408, 629409536, 632053760),
+    (232954624, 230591488, 232349952), (675349504, 669731072, 674744832),
+    (235622912, 230591488, 232624128), (678017792, 669731072, 675019008),
+    (4577942528, 4275505152, 4500556800), (13556577280, 12837462016, 13479191552),
+    (4919483392, 4275505152, 4535651328), (13898118144, 12837462016, 13514286080)]
+WORKSPACE_MULTI = [
+    (0, 0, 0), (0, 0, 0),
+    (95188736, 94006784, 94886144), (96523008, 94006784, 95023360),
+    (121112832, 118749696, 120508160), (123781120, 118749696, 120782336),
+    (8392452096, 8090014720, 8315066368), (8733992960, 8090014720, 8350160896),
+    (0, 0, 0), (0, 0, 0),
+    (94798592, 93616640, 94496000), (96132864, 93616640, 94633216),
+    (120332800, 117969664, 119728128), (123001088, 117969664, 120002304),
+    (8292642816, 7990205440, 8215257088), (8634183680, 7990205440, 8250351616)]
+
+
 def test_packed_record_size_matches_python_layout():
     """pp_packed_record_size (a host function) agrees with _abi.packed_dtype for every flag
     set, COCO and dense skeletons; compact records are at least 2x smaller than pp_ann."""
