@@ -397,7 +397,7 @@ struct Scratch {
 // one image: CifCaf.__call__ (cifcaf.py:67-122) with the front stages' host twins
 int decode_image(const float *cif, const float *caf, int K, int C, int H, int W,
                  const int32_t *skeleton, const pp_config &cfg, const BySource &bs,
-                 pp_ann *out, int cap, int32_t *count, int32_t *status, Scratch &S) {
+                 pp_ann *out, int cap, int32_t *count, int32_t *status, Scratch &S, int img) {
     const int64_t hw = (int64_t)H * W;
     const int64_t hh = pp::hr_dim(H, cfg.stride), ww = pp::hr_dim(W, cfg.stride);
     const int64_t pitch = (ww + 31) / 32 * 32;
@@ -443,6 +443,7 @@ int decode_image(const float *cif, const float *caf, int K, int C, int H, int W,
         pp_ann a;
         std::memset(&a, 0, sizeof(a));
         a.n_keypoints = K;
+        a.image = img;  // as the device decode sets it (include/pifpaf_amd.h)
         a.data[sd.field][0] = sd.x;
         a.data[sd.field][1] = sd.y;
         a.data[sd.field][2] = sd.v;
@@ -520,7 +521,7 @@ int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32
             const int rc = decode_image(cif + (int64_t)img * K * 5 * hw, caf + (int64_t)img * C * 9 * hw,
                                         K, C, H, W, skeleton, *cfg, bs,
                                         anns + (int64_t)img * ann_capacity, ann_capacity,
-                                        counts + img, status + img, S);
+                                        counts + img, status + img, S, img);
             if (rc != PP_OK) err.store(rc);
         }
     };

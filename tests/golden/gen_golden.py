@@ -37,6 +37,10 @@ Fixtures:
                        per-field sums + windows, full seed list, CafScored counts + digests,
                        full annotation lists (data, joint_scales, score, decoding_order,
                        frontier_order)
+  kc_<case>_<tag>_<mode>.npz  keypoint counts and skeletons other than COCO's
+                       (tests/kc_util.py CASES): the keys of decode_<case>.npz with the arrays
+                       sized by the stored K, on uniform_kc / planted_kc fields, and one
+                       multi-scale (ms2) decode in the keys of multi_<case>.npz
   meta.json            NumPy / Cython versions and SIMD dispatch of the generating host
 """
 import hashlib
@@ -51,7 +55,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.abspath(os.path.join(HERE, '..', '..'))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'oracle'))
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 
+import kc_util  # noqa: E402  pylint: disable=wrong-import-position
 import ref_loader  # noqa: E402  pylint: disable=wrong-import-position
 from openpifpaf_amd import constants, synthetic  # noqa: E402  pylint: disable=wrong-import-position
 from openpifpaf_amd._abi import EVAL_CONFIG, PREDICT_CONFIG  # noqa: E402  pylint: disable=wrong-import-position
@@ -115,15 +121,15 @@ def configure(decoder, mode, extra):
     decoder.nms.Keypoints.keypoint_threshold = c['nms_keypoint_threshold']
 
 
-def ann_arrays(anns, n_caf):
+def ann_arrays(anns, n_caf, k=17):
     """Annotation list -> data, scales, score, decoding / frontier order arrays."""
     out = {}
     n = len(anns)
-    out['ann_data'] = np.array([a.data for a in anns], np.float32).reshape(n, 17, 3)
-    out['ann_joint_scales'] = np.array([a.joint_scales for a in anns], np.float32).reshape(n, 17)
+    out['ann_data'] = np.array([a.data for a in anns], np.float32).reshape(n, k, 3)
+    out['ann_joint_scales'] = np.array([a.joint_scales for a in anns], np.float32).reshape(n, k)
     out['ann_score'] = np.array([a.score() for a in anns], np.float64)
-    dec_pairs = np.full((n, 17, 2), -1, np.int16)
-    dec_xyv = np.zeros((n, 17, 6), np.float32)
+    dec_pairs = np.full((n, k, 2), -1, np.int16)
+    dec_xyv = np.zeros((n, k, 6), np.float32)
     fr = np.full((n, 4 * n_caf, 2), -1, np.int16)
     for i, a in enumerate(anns):
         for t, (j1, j2, x1, x2) in enumerate(a.decoding_order):
@@ -185,7 +191,7 @@ def run_case(op, name, gen, h, w, seed, mode, skel_name, extra):
     out.update(ann_arrays(anns, len(skeleton)))
     np.savez_compressed(os.path.join(HERE, 'decode_%s.npz' % name), **out)
     print('%-22s seeds %5d  caf_a %6d  caf_b %7d  anns %4d' % (
-        name, len(seeds), out['caf_a_fwd_counts'].sum(), out['caf_b_fwd_counts'].sum(), n))
+        name, len(seeds), out['caf_a_fwd_counts'].sum(), out['caf_b_fwd_counts'].sum(), len(anns)))
 
 
 def gen_primitives(op):
@@ -830,6 +836,77 @@ def gen_confscales(op):
     decoder.CifSeeds.threshold = None
 
 
+def caf_entries(out, tag, cs):
+    out['caf_%s_fwd_counts' % tag] = np.array([f.shape[1] for f in cs.forward], np.int32)
+    out['caf_%s_bwd_counts' % tag] = np.array([b.shape[1] for b in cs.backward], np.int32)
+    out['caf_%s_fwd_sha' % tag] = np.array([sha(f) for f in cs.forward])
+    out['caf_%s_bwd_sha' % tag] = np.array([sha(b) for b in cs.backward])
+
+
+def gen_kc(op):
+    """The reference decoder at keypoint counts and skeletons other than COCO's
+    (tests/kc_util.py): per case one uniform 20x23 eval fixture and one planted predict
+    fixture, 'max' and 'greedy' variants for two cases, and one ms2 multi-scale decode."""
+    decoder = __import__('openpifpaf').decoder
+    for fx in kc_util.fixture_list():
+        name, tag, mode = fx
+        k, skeleton = kc_util.case(name)
+        kps = kc_util.keypoint_names(k)
+        gen = {'u': 'uniform', 'p': 'planted'}[tag[0]]
+        h, w = (int(t) for t in tag[1:].split('x'))
+        extra = {'max': {'connection_method': 'max'}, 'greedy': {'greedy': True}}.get(mode, {})
+        configure(decoder, mode if mode == 'predict' else 'eval', extra)
+        seed = kc_util.UNIFORM_SEEDS.get(name, 0) if gen == 'uniform' else kc_util.PLANTED_SEED
+        cif, caf, _ = kc_util.inputs(name, gen, h, w, seed)
+        fc = decoder.FieldConfig()
+        hr = decoder.CifHr(fc).fill([cif, caf]).accumulated
+        seeds = decoder.CifSeeds(hr, fc).fill([cif, caf]).get()
+        anns = decoder.CifCaf(fc, keypoints=kps, skeleton=skeleton)([cif, caf])
+        out = {
+            'case': np.array(name), 'K': k, 'generator': np.array(gen), 'H': h, 'W': w,
+            'seed': seed, 'mode': np.array(mode if mode == 'predict' else 'eval'),
+            'skeleton': np.asarray(skeleton, np.int32),
+            'n_people': kc_util.PLANTED_OBJECTS,
+            'connection_method': np.array(extra.get('connection_method', 'blend')),
+            'greedy': int(extra.get('greedy', False)),
+            'input_sha': np.array(sha(cif, caf)),
+            'cifhr_sha': np.array(sha(hr)),
+            'cifhr_field_sums': hr.astype(np.float64).sum(axis=(1, 2)),
+            'seeds': np.array([tuple(float(t) for t in s) for s in seeds],
+                              np.float32).reshape(-1, 5),
+        }
+        for t, th in (('a', None), ('b', 0.0001)):
+            caf_entries(out, t, decoder.CafScored(hr, fc, skeleton, score_th=th).fill([cif, caf]))
+        out.update(ann_arrays(anns, len(skeleton), k))
+        np.savez_compressed(kc_util.fixture_path(fx), **out)
+        print('kc %-28s seeds %5d  caf_a %6d  anns %4d  max frontier %3d' % (
+            kc_util.fixture_id(fx), len(seeds), out['caf_a_fwd_counts'].sum(), len(anns),
+            max([len(a.frontier_order) for a in anns], default=0)))
+
+    name, multi, mode = kc_util.MULTI_FIXTURE
+    k, skeleton = kc_util.case(name)
+    fields, kw = kc_util.multi_case(name, multi)
+    configure(decoder, mode, {})
+    fc = decoder.FieldConfig(**kw)
+    hr = decoder.CifHr(fc).fill(fields).accumulated
+    seeds = decoder.CifSeeds(hr, fc).fill(fields).get()
+    anns = decoder.CifCaf(fc, keypoints=kc_util.keypoint_names(k), skeleton=skeleton)(fields)
+    out = {
+        'case': np.array(name), 'K': k, 'name': np.array(multi), 'mode': np.array(mode),
+        'skeleton': np.asarray(skeleton, np.int32),
+        'connection_method': np.array('blend'), 'greedy': 0,
+        'input_sha': np.array(sha(*fields)),
+        'cifhr_sha': np.array(sha(hr)), 'cifhr_shape': np.array(hr.shape),
+        'seeds': np.array([[float(t) for t in sd] for sd in seeds], np.float32).reshape(-1, 5),
+    }
+    for t, th in (('a', None), ('b', 0.0001)):
+        caf_entries(out, t, decoder.CafScored(hr, fc, skeleton, score_th=th).fill(fields))
+    out.update(ann_arrays(anns, len(skeleton), k))
+    np.savez_compressed(kc_util.fixture_path(kc_util.MULTI_FIXTURE), **out)
+    print('kc multi', name, multi, mode, hr.shape, 'seeds', len(seeds), 'anns', len(anns))
+    decoder.CifSeeds.threshold = None
+
+
 def main():
     op = ref_loader.load()
     import Cython  # pylint: disable=import-outside-toplevel
@@ -874,6 +951,9 @@ def main():
     if only == ['detm']:
         gen_det_multi(op)
         return
+    if only == ['kc']:
+        gen_kc(op)
+        return
     gen_primitives(op)
     gen_errors()
     gen_nms(op)
@@ -886,6 +966,7 @@ def main():
     gen_multi(op)
     gen_api(op)
     gen_confscales(op)
+    gen_kc(op)
     for case in CASES:
         if only and case[0] not in only:
             continue

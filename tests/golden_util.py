@@ -74,11 +74,26 @@ def load_errors():
         return json.load(fh)
 
 
+def fixture_k(g, k=None):
+    """Number of keypoints of a fixture: its stored `K` (the kc_*.npz fixtures), else 17."""
+    if k is not None:
+        return k
+    return int(g['K']) if 'K' in g else 17
+
+
 def case_inputs(g):
     gen = str(g['generator'])
     h, w, seed = int(g['H']), int(g['W']), int(g['seed'])
     skeleton = [tuple(int(t) for t in e) for e in g['skeleton']]
-    if gen == 'zero':
+    if 'K' in g:  # tests/kc_util.py generators, any number of keypoints
+        import kc_util
+        k = int(g['K'])
+        if gen == 'uniform':
+            cif, caf = kc_util.uniform_kc(k, len(skeleton), h, w, seed)
+        else:
+            cif, caf = kc_util.planted_kc(k, skeleton, h, w, n_objects=int(g['n_people']),
+                                          seed=seed)
+    elif gen == 'zero':
         cif = np.zeros((17, 5, h, w), np.float32)
         caf = np.zeros((len(skeleton), 9, h, w), np.float32)
     elif gen == 'uniform':
@@ -154,8 +169,9 @@ def seeds_as_rows(seeds):
                      seeds['s']], axis=1).astype(np.float32)
 
 
-def compare_annotations(g, recs, k=17, stats=None):
-    """Compare pp_ann records with the golden annotation list.
+def compare_annotations(g, recs, k=None, stats=None):
+    """Compare pp_ann records with the golden annotation list (k keypoints: the fixture's
+    stored `K`, 17 where it stores none).
 
     Connectivity (decoding_order / frontier_order pairs) must match exactly; x / y of the
     keypoints and of the decoding_order xyv copies within XY_ULPS; v and joint scales within
@@ -163,6 +179,7 @@ def compare_annotations(g, recs, k=17, stats=None):
     (empty = parity); `stats` (a dict, optional) receives the largest deviations seen.
     """
     errs = []
+    k = fixture_k(g, k)
     n = len(g['ann_score'])
     if stats is None:
         stats = {}

@@ -1106,13 +1106,15 @@ def test_fetch_async_two_deep():
 
 # ---- compact records (pp_pack_compact) -----------------------------------------------------
 
-def _compact_vs_full(recs_full, recs_c, k=17):
+def _compact_vs_full(recs_full, recs_c, k=17, skeleton=None):
+    """k keypoints and `skeleton` (default: COCO's) of the decode both record sets are of."""
     from openpifpaf_amd import constants
     from openpifpaf_amd.annotation import Annotation
     from openpifpaf_amd._abi import PP_PACK_REFETCH
     assert len(recs_full) == len(recs_c)
     assert not (recs_c['n_decoding'] & PP_PACK_REFETCH).any()
-    kps, sk = constants.COCO_KEYPOINTS[:k], constants.COCO_PERSON_SKELETON
+    kps = constants.COCO_KEYPOINTS[:k] if k <= 17 else ['kp%d' % (j + 1) for j in range(k)]
+    sk = constants.COCO_PERSON_SKELETON if skeleton is None else skeleton
     for rf, rc in zip(recs_full, recs_c):
         a, b = Annotation.from_record(rf, kps, sk), Annotation.from_packed(rc, kps, sk)
         assert a.data.tobytes() == b.data.tobytes()
