@@ -466,6 +466,32 @@ int pp_fields_from_conv_ex(const void *d_conv, int32_t conv_dtype, int32_t n_img
                            float *d_out, int32_t out_fields, int32_t out_field0, void *stream);
 
 /*
+ * pp_fields_from_conv_ex on a view of a larger or differently ordered tensor, read in place:
+ * the result is, bit for bit, that of pp_fields_from_conv_ex on the dense
+ * (n_img, channels, h, w) copy of the same values, with channels = n_fields * (5 | 9 | 7) *
+ * 4^quad.
+ *   d_conv        element (0, 0, 0, 0) of the view; aligned to its element size, no more
+ *   conv_strides  host (4): the image, channel, row and column strides in elements.  The
+ *                 stride of a dimension of extent 1 is ignored.
+ * The view must be one of
+ *   planar       column stride 1, any image / channel / row strides: a dense NCHW tensor
+ *                and its channel, batch and spatial slices (one thread per output pixel,
+ *                as pp_fields_from_conv_ex)
+ *   interleaved  channel stride 1, any image / row / column strides: a channels-last (NHWC)
+ *                tensor and its slices (a workgroup reads the channel runs of 16 conv
+ *                pixels with 16-byte loads and transposes them in LDS)
+ * A view that is both (one column, or one channel) is read either way.  Checked before any
+ * launch, after the checks of pp_fields_from_conv_ex: a negative stride, or neither the
+ * channel nor the column stride equal to 1 -> PP_EINVAL.  Offsets are 64-bit.
+ */
+int pp_fields_from_conv_strided(const void *d_conv, int32_t conv_dtype,
+                                const int64_t *conv_strides, int32_t n_img, int32_t n_fields,
+                                int32_t layout, int32_t h, int32_t w, int32_t quad,
+                                int32_t mirror, const int32_t *src_field,
+                                const uint8_t *swap_ends, float *d_out, int32_t out_fields,
+                                int32_t out_field0, void *stream);
+
+/*
  * nms.Keypoints.annotations (nms.py:17-57) over caller records, n_img independent groups:
  * d_anns (n_img, ann_capacity) with d_counts[i] records in group i (modified in place as
  * the reference modifies its Annotation objects: joints below keypoint_threshold zeroed,

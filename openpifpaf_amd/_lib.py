@@ -101,6 +101,8 @@ _SIGNATURES = {
     'pp_fields_from_conv': ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], ctypes.c_int),
     'pp_fields_from_conv_ex': ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                 _vp, _i32, _i32, _vp], ctypes.c_int),
+    'pp_fields_from_conv_strided': ([_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                     _vp, _vp, _vp, _i32, _i32, _vp], ctypes.c_int),
     'pp_nms_keypoints': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
                          ctypes.c_int),
     'pp_nms_keypoints_scored': ([_vp, _vp, _i32, _i32, _i32, _vp, _f64, _vp, _vp, _vp, _vp,

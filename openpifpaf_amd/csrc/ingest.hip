@@ -16,6 +16,12 @@
 // Work unit: one thread per output pixel of one (image, field); it writes every output
 // channel of that field.  Reads and writes are coalesced along x (a mirrored wave reads
 // the same contiguous segment, back to front).
+//
+// pp_fields_from_conv_strided reads a view by its strides.  A view whose columns are
+// adjacent (NCHW and its slices) keeps that work unit.  A view whose channels are adjacent
+// (channels-last and its slices) goes through ingest_interleaved_kernel: a workgroup loads
+// the channel runs of 16 conv pixels of one row, lanes along the channels, transposes them
+// in LDS and writes with lanes along X, as the planar kernel does.
 #include <hip/hip_fp16.h>
 
 #include "pp_common.hpp"
@@ -58,6 +64,24 @@ __device__ __forceinline__ float load_f32(const Bf16 *p) {
     return __uint_as_float((uint32_t)p->bits << 16);
 }
 
+// what the head and its collector do to one conv value (both kernels call this)
+__device__ __forceinline__ float ingest_value(int op, float v, bool mirror, int X, int Y) {
+    float r;
+    switch (op) {
+        case 1: r = (float)(1.0 / (1.0 + exp(-(double)v))); break;  // torch.sigmoid
+        case 2: r = (float)exp((double)v); break;                  // torch.exp
+        case 3: r = (mirror ? -v : v) + (float)X; break;           // + index_field x
+        case 4: r = v + (float)Y; break;                           // + index_field y
+        default: r = v;
+    }
+    return r;
+}
+
+// element strides of a conv view (pp_fields_from_conv_strided)
+struct IngestStrides {
+    int64_t img, ch, row, col;
+};
+
 template <typename T, bool kEx>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a, IngestFlip t) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -91,26 +115,216 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a, IngestFlip t)
         if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
         const int64_t ch = (int64_t)(a.grp_off[o] + fs * a.fld_mul[o] + comp) * mul + sub;
         const float v = load_f32(src + ch * a.h * a.w);
-        float r;
-        switch (op) {
-            case 1: r = (float)(1.0 / (1.0 + exp(-(double)v))); break;  // torch.sigmoid
-            case 2: r = (float)exp((double)v); break;                  // torch.exp
-            case 3: r = (mirror ? -v : v) + (float)X; break;           // + index_field x
-            case 4: r = v + (float)Y; break;                           // + index_field y
-            default: r = v;
-        }
-        dst[(int64_t)o * HW] = r;
+        dst[(int64_t)o * HW] = ingest_value(op, v, mirror, X, Y);
     }
 }
 
+// ingest_kernel on a view with adjacent columns and any image / channel / row strides
+template <typename T, bool kEx>
+__global__ __launch_bounds__(256) void ingest_strided_kernel(IngestArgs a, IngestFlip t,
+                                                             IngestStrides s) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t HW = (int64_t)a.H * a.W;
+    const int f = blockIdx.y, img = blockIdx.z;
+    if (pix >= HW) return;
+    const int Y = (int)(pix / a.W), X = (int)(pix % a.W);
+    int fs = f;
+    bool mirror = false, swap = false;
+    if (kEx) {
+        mirror = t.mirror != 0;
+        if (t.has_src) fs = t.src_field[f];
+        swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);
+    }
+    // undo the dequads: T_q[c, Y, X] = T_{q-1}[4c + 2(Y&1) + (X&1), Y>>1, X>>1], so the
+    // conv channel is 4^quad * c + sub with the finest level's offset the most significant
+    int sub = 0, y0 = Y, x0 = mirror ? a.W - 1 - X : X, mul = 1;
+    for (int q = 0; q < a.quad; q++) {
+        sub = 4 * sub + (2 * (y0 & 1) + (x0 & 1));
+        mul *= 4;
+        y0 >>= 1;
+        x0 >>= 1;
+    }
+    const T *src = (const T *)a.conv + (int64_t)img * s.img + (int64_t)y0 * s.row + x0;
+    float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW + pix;
+    for (int o = 0; o < a.n_out; o++) {
+        const int op = a.op[o];
+        int comp = a.comp[o];
+        // the end points trade places in the regressions only (heads.py:209-212); CAF's
+        // four vector components are exactly its ops 3 / 4
+        if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
+        const int64_t ch = (int64_t)(a.grp_off[o] + fs * a.fld_mul[o] + comp) * mul + sub;
+        const float v = load_f32(src + ch * s.ch);
+        dst[(int64_t)o * HW] = ingest_value(op, v, mirror, X, Y);
+    }
+}
+
+// ---- channels adjacent in memory (channels-last and its slices) ----
+//
+// Tile: kTilePix conv pixels of one conv row of one image, and a chunk of whole pre-dequad
+// channels (chunk_base of them = chunk_base * 4^quad conv channels <= kMaxChunkCh).  The
+// tile owns the 2^quad output rows and kTilePix * 2^quad output columns of those pixels
+// for every (field, output channel) whose conv channels are in the chunk.
+//
+// LDS image: float32 [pixel][channel of the chunk], pixel pitch `lds_pitch` = 2 (mod 32)
+// floats.  On the store side lanes run along X; at quad 1 two adjacent lanes are the two
+// channels sub, sub + 1 of one pixel and the next pair is the next pixel, so 32 lanes
+// read banks 2k + {0, 1}, k = 0..15: all 32 banks of a ds_read_b32 lane group once.
+constexpr int kTilePix = 16;
+constexpr int kMaxChunkCh = 512;
+constexpr int kLdsFloats = kTilePix * (kMaxChunkCh + 2);  // pitch <= kMaxChunkCh + 2
+
+struct IngestTile {
+    int chunk_base;  // pre-dequad channels per chunk (blockIdx.y counts chunks)
+    int lds_pitch;   // floats between two pixels of the LDS image
+    int tiles_x;     // tiles per conv row (blockIdx.x = row * tiles_x + tile)
+};
+
+__device__ __forceinline__ float bits_f32(const float *, uint32_t b) { return __uint_as_float(b); }
+__device__ __forceinline__ float bits_f32(const __half *, uint32_t b) {
+    return __half2float(__ushort_as_half((unsigned short)b));
+}
+__device__ __forceinline__ float bits_f32(const Bf16 *, uint32_t b) {
+    return __uint_as_float(b << 16);
+}
+
+// one 16-byte vector of the run -> its 4 or 8 float32 values in the LDS row
+__device__ __forceinline__ void spill_vec(const float *tag, uint4 v, float *row) {
+    row[0] = bits_f32(tag, v.x);
+    row[1] = bits_f32(tag, v.y);
+    row[2] = bits_f32(tag, v.z);
+    row[3] = bits_f32(tag, v.w);
+}
 template <typename T>
-static void launch_ingest(const IngestArgs &a, const IngestFlip &t, bool ex, hipStream_t stream) {
+__device__ __forceinline__ void spill_vec(const T *tag, uint4 v, float *row) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    for (int j = 0; j < 4; j++) {
+        row[2 * j] = bits_f32(tag, w[j] & 0xffffu);
+        row[2 * j + 1] = bits_f32(tag, w[j] >> 16);
+    }
+}
+
+template <typename T, bool kEx>
+__global__ __launch_bounds__(256) void ingest_interleaved_kernel(IngestArgs a, IngestFlip t,
+                                                                 IngestStrides s, IngestTile g) {
+    __shared__ float lds[kLdsFloats];
+    constexpr int kVec = 16 / (int)sizeof(T);  // elements per 16-byte load
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int img = blockIdx.z;
+    const int y0 = blockIdx.x / g.tiles_x, x0t = (blockIdx.x % g.tiles_x) * kTilePix;
+    const int shift = 2 * a.quad;
+    const int cb0 = blockIdx.y * g.chunk_base;  // first pre-dequad channel of the chunk
+    const int n_base = (int)(a.conv_ch >> shift);
+    const int cb1 = min(cb0 + g.chunk_base, n_base);
+    const int n = (cb1 - cb0) << shift;  // conv channels of the chunk
+    const int n_pix = min(kTilePix, a.w - x0t);
+
+    // load: one wave per pixel, lanes along its channel run; 16-byte loads between the
+    // run's first and last 16-byte boundary, single elements before and after (a slice at
+    // an odd channel offset is aligned to its element only).  All of a wave's loads are
+    // issued before its first LDS write, so that they are in flight together: kPix pixels,
+    // each at most kIter vectors and two elements a lane.
+    constexpr int kPix = kTilePix / 4, kIter = kMaxChunkCh / kVec / 64;
+    const T *run[kPix];
+    int head[kPix], n_vec[kPix];
+    uint4 vec[kPix][kIter];
+    float first[kPix], last[kPix];
+#pragma unroll
+    for (int i = 0; i < kPix; i++) {
+        const int p = wave + 4 * i;
+        n_vec[i] = head[i] = 0;
+        if (p >= n_pix) continue;
+        run[i] = (const T *)a.conv + (int64_t)img * s.img + (int64_t)y0 * s.row +
+                 (int64_t)(x0t + p) * s.col + ((int64_t)cb0 << shift);
+        const int to_boundary = (int)((16 - ((uintptr_t)run[i] & 15)) & 15) / (int)sizeof(T);
+        head[i] = min(to_boundary, n);
+        n_vec[i] = (n - head[i]) / kVec;
+        if (lane < head[i]) first[i] = load_f32(run[i] + lane);
+#pragma unroll
+        for (int j = 0; j < kIter; j++)
+            if (lane + 64 * j < n_vec[i])
+                vec[i][j] = *reinterpret_cast<const uint4 *>(run[i] + head[i] +
+                                                             (lane + 64 * j) * kVec);
+        const int c = head[i] + n_vec[i] * kVec + lane;
+        if (c < n) last[i] = load_f32(run[i] + c);
+    }
+#pragma unroll
+    for (int i = 0; i < kPix; i++) {
+        const int p = wave + 4 * i;
+        if (p >= n_pix) continue;
+        float *row = lds + p * g.lds_pitch;
+        if (lane < head[i]) row[lane] = first[i];
+#pragma unroll
+        for (int j = 0; j < kIter; j++)
+            if (lane + 64 * j < n_vec[i])
+                spill_vec(run[i], vec[i][j], row + head[i] + (lane + 64 * j) * kVec);
+        const int c = head[i] + n_vec[i] * kVec + lane;
+        if (c < n) row[c] = last[i];
+    }
+    __syncthreads();
+
+    // store: lanes along X, then the tile's output rows, then the fields
+    const int64_t HW = (int64_t)a.H * a.W;
+    const bool mirror = kEx && t.mirror != 0;
+    const int x_bits = 4 + a.quad;  // kTilePix << quad output columns
+    static_assert(kTilePix == 16, "x_bits assumes 16 pixels per tile");
+    const int n_work = a.n_fields << (x_bits + a.quad);
+    for (int e = tid; e < n_work; e += 256) {
+        const int xl = e & ((1 << x_bits) - 1);
+        const int yr = (e >> x_bits) & ((1 << a.quad) - 1);
+        const int f = e >> (x_bits + a.quad);
+        const int xs = (x0t << a.quad) + xl;  // source column after the dequads
+        const int Y = (y0 << a.quad) + yr;
+        if (xs >= a.W || Y >= a.H) continue;  // the crop of the last row / column
+        const int X = mirror ? a.W - 1 - xs : xs;
+        int fs = f;
+        bool swap = false;
+        if (kEx) {
+            if (t.has_src) fs = t.src_field[f];
+            swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);
+        }
+        int sub = 0, yy = Y, xx = xs;
+        for (int q = 0; q < a.quad; q++) {
+            sub = 4 * sub + (2 * (yy & 1) + (xx & 1));
+            yy >>= 1;
+            xx >>= 1;
+        }
+        const float *src = lds + (xl >> a.quad) * g.lds_pitch + sub;
+        float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW +
+                     (int64_t)Y * a.W + X;
+        for (int o = 0; o < a.n_out; o++) {
+            const int op = a.op[o];
+            int comp = a.comp[o];
+            if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
+            const int cb = a.grp_off[o] + fs * a.fld_mul[o] + comp;
+            if (cb < cb0 || cb >= cb1) continue;  // another chunk's workgroup writes it
+            dst[(int64_t)o * HW] = ingest_value(op, src[(cb - cb0) << shift], mirror, X, Y);
+        }
+    }
+}
+
+enum Route { kDense, kPlanar, kInterleaved };
+
+template <typename T>
+static void launch_ingest(Route route, const IngestArgs &a, const IngestFlip &t,
+                          const IngestStrides &s, const IngestTile &g, int n_chunks, bool ex,
+                          hipStream_t stream) {
     const int64_t HW = (int64_t)a.H * a.W;
     const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)a.n_fields, (unsigned)a.n_img);
-    if (ex)
+    const dim3 tiles((unsigned)(a.h * g.tiles_x), (unsigned)n_chunks, (unsigned)a.n_img);
+    if (route == kDense && ex)
         hipLaunchKernelGGL((ingest_kernel<T, true>), grid, dim3(256), 0, stream, a, t);
-    else
+    else if (route == kDense)
         hipLaunchKernelGGL((ingest_kernel<T, false>), grid, dim3(256), 0, stream, a, t);
+    else if (route == kPlanar && ex)
+        hipLaunchKernelGGL((ingest_strided_kernel<T, true>), grid, dim3(256), 0, stream, a, t, s);
+    else if (route == kPlanar)
+        hipLaunchKernelGGL((ingest_strided_kernel<T, false>), grid, dim3(256), 0, stream, a, t, s);
+    else if (ex)
+        hipLaunchKernelGGL((ingest_interleaved_kernel<T, true>), tiles, dim3(256), 0, stream, a,
+                           t, s, g);
+    else
+        hipLaunchKernelGGL((ingest_interleaved_kernel<T, false>), tiles, dim3(256), 0, stream, a,
+                           t, s, g);
 }
 
 }  // namespace pp
@@ -124,8 +338,9 @@ int64_t pp_fields_dim(int64_t n, int32_t quad) {
     return n;
 }
 
+// conv_strides NULL: the dense (n_img, channels, h, w) tensor of the two older symbols
 static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dtype,
-                            int32_t n_img, int32_t n_fields, int32_t layout, int32_t h,
+                            const int64_t *conv_strides, int32_t n_img, int32_t n_fields, int32_t layout, int32_t h,
                             int32_t w, int32_t quad, int32_t mirror, const int32_t *src_field,
                             const uint8_t *swap_ends, float *d_out, int32_t out_fields,
                             int32_t out_field0, void *stream) {
@@ -210,15 +425,52 @@ static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dt
             a.op[o] = 2;
         }
     }
-    if (n_img == 0) return PP_OK;
     // the plain f32 ingest keeps its own instantiation without the table reads
     const bool ex = t.mirror || t.has_src || t.swap_mask;
+    Route route = kDense;
+    IngestStrides s{};
+    IngestTile g{};
+    int n_chunks = 1;
+    if (conv_strides) {
+        // the stride of a dimension of extent 1 says nothing (torch reports any value)
+        const int64_t extent[4] = {n_img, a.conv_ch, h, w};
+        int64_t st[4];
+        for (int d = 0; d < 4; d++) {
+            st[d] = extent[d] > 1 ? conv_strides[d] : 0;
+            if (st[d] < 0) return fail(PP_EINVAL, name + ": negative conv stride");
+        }
+        s = IngestStrides{st[0], st[1], st[2], st[3]};
+        if (s.ch == 1) {
+            route = kInterleaved;
+            // chunks of whole pre-dequad channels, as even as the LDS image allows
+            const int n_base = (int)(a.conv_ch >> (2 * quad));
+            const int most = kMaxChunkCh >> (2 * quad);  // >= 2: quad <= 4
+            n_chunks = (n_base + most - 1) / most;
+            g.tiles_x = (w + kTilePix - 1) / kTilePix;
+            if (n_chunks > 65535 || (int64_t)h * g.tiles_x > INT32_MAX)
+                return fail(PP_ESHAPE, name + ": conv too large for the interleaved grid");
+            g.chunk_base = (n_base + n_chunks - 1) / n_chunks;
+            const int ch = g.chunk_base << (2 * quad);
+            g.lds_pitch = ch + ((2 - ch) & 31);
+        } else if (w == 1 || s.col == 1) {
+            // a dense NCHW tensor is what ingest_kernel reads without the stride arguments
+            const bool dense = (h == 1 || s.row == w) &&
+                               s.ch == (a.conv_ch > 1 ? (int64_t)h * w : 0) &&
+                               (n_img <= 1 || s.img == a.conv_ch * h * w);
+            route = dense ? kDense : kPlanar;
+        } else {
+            return fail(PP_EINVAL, name + ": neither the channel stride (" + std::to_string(s.ch) +
+                        ") nor the column stride (" + std::to_string(s.col) + ") is 1");
+        }
+    }
+    if (n_img == 0) return PP_OK;
+    const hipStream_t hs = (hipStream_t)stream;
     if (conv_dtype == PP_DTYPE_F32)
-        launch_ingest<float>(a, t, ex, (hipStream_t)stream);
+        launch_ingest<float>(route, a, t, s, g, n_chunks, ex, hs);
     else if (conv_dtype == PP_DTYPE_F16)
-        launch_ingest<__half>(a, t, ex, (hipStream_t)stream);
+        launch_ingest<__half>(route, a, t, s, g, n_chunks, ex, hs);
     else
-        launch_ingest<Bf16>(a, t, ex, (hipStream_t)stream);
+        launch_ingest<Bf16>(route, a, t, s, g, n_chunks, ex, hs);
     return check_launch(who);
 }
 
@@ -226,14 +478,26 @@ int pp_fields_from_conv_ex(const void *d_conv, int32_t conv_dtype, int32_t n_img
                            int32_t n_fields, int32_t layout, int32_t h, int32_t w, int32_t quad,
                            int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
                            float *d_out, int32_t out_fields, int32_t out_field0, void *stream) {
-    return fields_from_conv("pp_fields_from_conv_ex", d_conv, conv_dtype, n_img, n_fields,
+    return fields_from_conv("pp_fields_from_conv_ex", d_conv, conv_dtype, nullptr, n_img, n_fields,
                             layout, h, w, quad, mirror, src_field, swap_ends, d_out, out_fields,
                             out_field0, stream);
 }
 
+int pp_fields_from_conv_strided(const void *d_conv, int32_t conv_dtype,
+                                const int64_t *conv_strides, int32_t n_img, int32_t n_fields,
+                                int32_t layout, int32_t h, int32_t w, int32_t quad,
+                                int32_t mirror, const int32_t *src_field,
+                                const uint8_t *swap_ends, float *d_out, int32_t out_fields,
+                                int32_t out_field0, void *stream) {
+    if (!conv_strides) return fail(PP_EINVAL, "pp_fields_from_conv_strided: NULL argument");
+    return fields_from_conv("pp_fields_from_conv_strided", d_conv, conv_dtype, conv_strides,
+                            n_img, n_fields, layout, h, w, quad, mirror, src_field, swap_ends,
+                            d_out, out_fields, out_field0, stream);
+}
+
 int pp_fields_from_conv(const float *d_conv, int32_t n_img, int32_t n_fields, int32_t layout,
                         int32_t h, int32_t w, int32_t quad, float *d_out, void *stream) {
-    return fields_from_conv("pp_fields_from_conv", d_conv, PP_DTYPE_F32, n_img, n_fields,
+    return fields_from_conv("pp_fields_from_conv", d_conv, PP_DTYPE_F32, nullptr, n_img, n_fields,
                             layout, h, w, quad, 0, nullptr, nullptr, d_out, n_fields, 0, stream);
 }
 

@@ -8,6 +8,8 @@ for a model whose heads stop at their conv: forward(conv outputs) -> (cif, caf).
 
 The same pass reads float16 / bfloat16 conv outputs directly and undoes the horizontal
 flip of a mirrored pass (heads.PifHFlip / PafHFlip, heads.py:145-214; pp_fields_from_conv_ex).
+Channels-last tensors and channel, batch or spatial slices of a larger tensor are read where
+they lie, by their strides (pp_fields_from_conv_strided).
 `MultiScaleCollector` does that for the head list of a ShellMultiScale-style model
 (network/nets.py:95-143), whose second five scales come from the mirrored image.
 """
@@ -74,22 +76,34 @@ def caf_hflip(keypoints, skeleton, hflip=constants.HFLIP):
     return HFlip(src_field, swap_ends)
 
 
+def _in_place(conv):
+    """Whether pp_fields_from_conv_strided reads this (B, C, h, w) tensor as it lies: its
+    columns or its channels are adjacent (the stride of an extent-1 dimension says nothing)."""
+    stride = [s if n > 1 else 0 for s, n in zip(conv.stride(), conv.shape)]
+    return min(stride) >= 0 and (stride[1] == 1 or stride[3] == 1 or conv.shape[3] == 1)
+
+
 def fields_from_conv(conv, n_fields, kind, quad=1, hflip=None, out=None, out_field0=0):
     """conv (B, n_fields * per_field * 4^quad, h, w) -> decoder fields (B, n_fields,
     5 | 9 | 7, H, W) float32 for kind 'cif' | 'caf' | 'cifdet'.
 
     A float32, float16 or bfloat16 device tensor is read as it is (no float32 copy of a
-    half tensor); anything else becomes a float32 device tensor first.  `hflip` (an HFlip:
-    cif_hflip / caf_hflip, or HFlip() for a CifDet head) undoes the horizontal flip of a
-    head computed from a mirrored image in the same pass.  With `out` (a contiguous float32
+    half tensor); anything else becomes a float32 device tensor first.  It is also read where
+    it is (pp_fields_from_conv_strided): a tensor or view whose columns are adjacent in memory
+    (NCHW and its channel, batch and spatial slices) or whose channels are (channels-last
+    and its slices) is not copied.  Only a view that is neither, such as one with a step
+    along both the channels and the columns, is copied once with .contiguous().
+
+    `hflip` (an HFlip: cif_hflip / caf_hflip, or HFlip() for a CifDet head) undoes the
+    horizontal flip of a head computed from a mirrored image in the same pass.  With `out` (a contiguous float32
     device tensor (B, out_fields, n_out, H, W)) the fields go to out[:, out_field0:
     out_field0 + n_fields], the rest of it is left alone and `out` is returned."""
     layout, n_out = LAYOUTS[kind]
-    if _device.is_device(conv) and conv.dtype in _DTYPES:
-        conv = conv.contiguous()
-    else:
+    if not (_device.is_device(conv) and conv.dtype in _DTYPES):
         conv = _device.to_device(conv)
     b, ch, h, w = conv.shape
+    if not _in_place(conv):
+        conv = conv.contiguous()
     if ch != n_fields * n_out * 4 ** quad:
         raise ValueError('{} conv expects {} channels, got {}'.format(
             kind, n_fields * n_out * 4 ** quad, ch))
@@ -104,9 +118,10 @@ def fields_from_conv(conv, n_fields, kind, quad=1, hflip=None, out=None, out_fie
         raise ValueError('out must be a contiguous float32 device tensor (B, out_fields, '
                          '{}, H, W) for this conv'.format(n_out))
     src_field, swap_ends = hflip.tables(n_fields) if hflip is not None else (None, None)
-    call('pp_fields_from_conv_ex', _device.ptr(conv), _DTYPES[conv.dtype], b, n_fields, layout,
-         h, w, quad, int(hflip is not None), src_field, swap_ends, _device.ptr(out),
-         out.shape[1], int(out_field0), _device.stream())
+    call('pp_fields_from_conv_strided', _device.ptr(conv), _DTYPES[conv.dtype],
+         (ctypes.c_int64 * 4)(*conv.stride()), b, n_fields, layout, h, w, quad,
+         int(hflip is not None), src_field, swap_ends, _device.ptr(out), out.shape[1],
+         int(out_field0), _device.stream())
     return out
 
 
