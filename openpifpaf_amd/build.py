@@ -60,15 +60,20 @@ def source_digest():
     return h.hexdigest()[:16]
 
 
-def _deps_mtime():
-    paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
+def _deps_mtime(src=None):
+    """Newest of what the library (src None) or the object of one source is built from: no
+    .hip includes another, so an object depends on its own .hip, every csrc/*.hpp and the
+    C header."""
+    paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if src is None or f.endswith('.hpp')]
     paths.append(os.path.join(REPO, 'include', 'pifpaf_amd.h'))
+    if src is not None:
+        paths.append(src)
     return max(os.path.getmtime(p) for p in paths)
 
 
 def _compile(src, bdir=BUILD, extra=()):
     obj = os.path.join(bdir, os.path.basename(src)[:-4] + '.o')
-    if os.path.exists(obj) and os.path.getmtime(obj) >= _deps_mtime():
+    if os.path.exists(obj) and os.path.getmtime(obj) >= _deps_mtime(src):
         return obj
     cmd = [HIPCC] + CFLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(extra) + ['-c', src, '-o', obj]
     res = subprocess.run(cmd, capture_output=True, text=True, check=False)
@@ -87,9 +92,11 @@ def build(force=False, verbose=True, variant=''):
         return lib
     # the diagnostic variant (never loaded by default): 'stamps' (in-kernel cycle stamps)
     extra = VARIANTS.get(variant, [])
-    workers = min(8, len(sources()))
-    with concurrent.futures.ThreadPoolExecutor(workers) as ex:
-        objs = list(ex.map(lambda src: _compile(src, bdir, extra), sources()))
+    # the largest sources start first (the seed loops, splat.hip and stages.hip take longest:
+    # none of them waits in the pool behind small files); the link keeps the order by name
+    queue = sorted(sources(), key=os.path.getsize, reverse=True)
+    with concurrent.futures.ThreadPoolExecutor(min(8, len(queue))) as ex:
+        objs = sorted(ex.map(lambda src: _compile(src, bdir, extra), queue))
     cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', lib] + objs
     res = subprocess.run(cmd, capture_output=True, text=True, check=False)
     if res.returncode != 0:

@@ -1,6 +1,6 @@
 // decode.hip — host side of the decoder: the workspace layout, the stage sequence of a
 // decode (decode_heads) and the pp_decode_* entry points.  The kernels and their
-// launchers are in grow.hip.
+// launchers are in seed_loop.hip, seed_loop_ext.hip, complete.hip and nms.hip.
 #include "grow_args.hpp"
 
 #include <stdio.h>
@@ -22,8 +22,10 @@ int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C
                         int *offs, const int *gate, bool index_only, hipStream_t s);
 void caf_bucket_grid(int H, int W, int stride, int *bw, int *bh, int *nb, float *inv_e);
 
-// the decoder's kernels (grow.hip)
+// the decoder's kernels, each launched from the file that defines it (seed_loop.hip,
+// seed_loop_ext.hip, complete.hip, nms.hip)
 int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s);
+int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s);
 int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s);
 int launch_nms(const GrowArgs &g, int n_img, bool wide, bool bitmap, hipStream_t s);
 
@@ -443,7 +445,8 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
         // PP_STAGE_SEED_LOOP_ONLY / PP_STAGE_AFTER_SEED_LOOP split stage 8 in two calls
         const bool run_rest = !(stages & PP_STAGE_SEED_LOOP_ONLY);
         if (!(stages & PP_STAGE_AFTER_SEED_LOOP)) {
-            rc = launch_seed_loop(g, n_img, s);
+            // external helper workgroups (images fewer than CUs) have a kernel of their own
+            rc = g.n_ext > 0 ? launch_seed_loop_ext(g, n_img, s) : launch_seed_loop(g, n_img, s);
             if (rc) return rc;
         }
         // PP_STAGE_COMPLETE_ONLY / PP_STAGE_NMS_ONLY split the rest once more

@@ -1,4 +1,4 @@
-// grow_args.hpp — what the CifCaf decoder's kernels (grow.hip, which has the overview) and
+// grow_args.hpp — what the CifCaf decoder's kernels (grow.hpp has the overview) and
 // its host side (decode.hip) share.  Constants, workspace records, GrowArgs, the
 // per-wave LDS record and the diagnostic build's stamp macros.
 #pragma once
@@ -69,7 +69,7 @@ constexpr int kSlots = 2 * PP_MAX_EDGES;   // directed edges (two lanes' worth o
 constexpr int kHeap = 2 * PP_MAX_EDGES + 8;
 constexpr int kOccMargin = 64;              // NMS occupancy slack beyond the main grid
 constexpr int kCompleteWays = 64;           // force-complete workgroups per image
-// the seed loop's workgroup, caches and external helpers (grow.hip has the design)
+// the seed loop's workgroup, caches and external helpers (seed_loop.hpp has the design)
 // 8 waves; 16 (cache 32, scan 256): 1.79 vs 1.28 ms per cfg3 step; 4 / 6: no better
 constexpr int kSeedWaves = 8;
 constexpr int kSpecCache = 16;     // speculative annotations of this CU's helpers

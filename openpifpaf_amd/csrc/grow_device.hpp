@@ -1,6 +1,6 @@
 // grow_device.hpp — the device helpers that more than one kernel file of the decoder uses
-// (grow.hip, nms.hip): readlane and the DPP wave reductions, the occupancy grid's geometry,
-// whole-record copies.
+// (the seed loops and force-complete through grow.hpp, nms.hip): readlane and the DPP wave
+// reductions, the occupancy grid's geometry, whole-record copies.
 #pragma once
 
 #include "grow_args.hpp"

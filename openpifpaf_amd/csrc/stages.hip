@@ -1049,7 +1049,7 @@ __device__ __forceinline__ int caf_bucket(float x, float y, int bw, int bh, floa
 
 // INDEX_ONLY (the force-complete set): bucket the cell index of every cell with c > th by
 // its source position and store nothing else.  The rescoring by CifHr and the second
-// threshold (caf_scored.py:63-81) are applied by the query (grow.hip, consider_raw) to the
+// threshold (caf_scored.py:63-81) are applied by the query (grow_connection.hpp, consider_raw) to the
 // few columns in its box; both filters commute with the bucketing and the tie-break key is
 // the cell index either way.
 //

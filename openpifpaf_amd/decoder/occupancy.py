@@ -1,6 +1,6 @@
 """Occupancy grid (decoder/occupancy.py:10-47) held in device memory.
 
-The decoder's own occupancy lives inside the seed-loop kernel (csrc/grow.hip).  This class
+The decoder's own occupancy lives inside the seed-loop kernel (csrc/seed_loop.hpp, csrc/grow.hpp).  This class
 serves callers of the reference API: the grid is a (fields, H / r, W / r) u8 device tensor,
 `set` marks boxes with pp_occupancy_set (decoder/utils.py:61-66 semantics: the box around
 the rounded reduced position, u8 add that wraps) and `get` reads with

@@ -2,7 +2,7 @@
 // bit, over the domains it is used on:
 //  - the CifHr fold: divisors d = sigma^2 in [1, 2^100], numerators n = -0.5 * (dx^2 + dy^2)
 //    with sum in [0.25, d] (plus NaN numerators);
-//  - the CAF score (grow.hip score_arg): d = sigma^2 in [1, 2^90], n = -0.5 d^2 with
+//  - the CAF score (grow_connection.hpp score_arg): d = sigma^2 in [1, 2^90], n = -0.5 d^2 with
 //    d^2 in [0, 128 sigma^2], log-uniform down to the subnormals, and exact zeros: the
 //    quotient bit for bit where |n| >= 2^-60, np.exp of it below (both quotients round
 //    np.exp to 1 there);

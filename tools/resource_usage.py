@@ -1,5 +1,5 @@
 """Kernel resource usage (VGPRs, spills, LDS, occupancy) from the compiler remarks:
-    python tools/resource_usage.py grow.hip seed_loop_kernel nms_kernel"""
+    python tools/resource_usage.py seed_loop.hip seed_loop_kernel spec_plan"""
 import os
 import subprocess
 import sys

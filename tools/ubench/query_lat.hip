@@ -1,4 +1,4 @@
-// Microbenchmark: cycles per flat_query (the seed loop's set-A query, grow.hip) and per
+// Microbenchmark: cycles per flat_query (the seed loop's set-A query, grow_columns.hpp) and per
 // connection evaluation (forward + reverse query) for one wave alone on the GPU, over a
 // synthetic 128-column set held in registers as eval_ahead holds it, with 1 / 4 / 16 / 64
 // columns inside the query box.  Tells the query's own latency apart from what the seed
@@ -6,7 +6,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include \
 //       tools/ubench/query_lat.hip -L openpifpaf_amd -lpifpaf_amd -o query_lat &&
 //   LD_LIBRARY_PATH=openpifpaf_amd ./query_lat
-#include "../../openpifpaf_amd/csrc/grow.hip"
+#include "../../openpifpaf_amd/csrc/grow_columns.hpp"
 
 #include <stdio.h>
 
