@@ -417,6 +417,78 @@ int pp_dets_inverse(pp_det *d_dets, const int32_t *d_counts, int32_t n_img, int3
                     const pp_inverse_meta *d_metas, void *stream);
 
 /*
+ * COCO prediction records, EvalCoco.from_predictions (eval_coco.py:108-158) for a whole
+ * batch: from a decode's records (NOT modified) and one meta per image to the records an
+ * evaluation writes to json, packed image after image.  Per image, in the reference's order:
+ *   1. Preprocess.annotations_inverse on every record (eval_coco.py:113; the arithmetic of
+ *      pp_annotations_inverse / pp_dets_inverse; d_hswap as there).  A NaN in x, y or v of
+ *      any record sets PP_COCO_NAN in the image's flag word (preprocess.py:67 asserts).
+ *   2. poses only, when small_threshold != 0: keep a record when
+ *      Annotation.scale(v_th=0.01) >= small_threshold (eval_coco.py:115-117,
+ *      annotation.py:73-80; float32 scale against the threshold rounded to float32, the
+ *      Python float 0.0 against the threshold in float64 when no joint has v > 0.01).
+ *   3. the first max_per_image survivors, in record order (eval_coco.py:118-120).
+ *   4. json_data() (annotation.py:82-119 / 138-145) with image_id (eval_coco.py:122-131):
+ *      keypoints with v of visible joints raised to 0.01, every value rounded to 2
+ *      decimals as a double; bbox_from_keypoints in float32, rounded to 2 decimals; score
+ *      max(0.001, round(score, 3)) of the record's score; a detection's category_id is
+ *      field + 1.  The doubles are the Python floats the reference dumps.
+ *   5. an image without a kept record gets one dummy record (eval_coco.py:133-141):
+ *      keypoints zero, bbox [0, 0, 1, 1], score 0.001, category_id 1; PP_COCO_EMPTY is set
+ *      in its flag word.
+ * Pose records have pp_coco_record_size(K) = 56 + 24 K bytes: the pp_coco_det head with
+ * n_keypoints (= K) in place of pad_, then double keypoints[K][3].
+ *   d_anns / d_dets  (n_img, capacity) records, d_counts (n_img); a count above capacity
+ *                    reads as capacity
+ *   d_image_ids      (n_img) int64
+ *   out              out_capacity records, 8-byte aligned; out_counts (n_img) = records of
+ *                    each image, the dummy included; out_flags (n_img) PP_COCO_* bits.  Each
+ *                    may be device memory or pinned host memory, as for pp_pack_compact.
+ *                    Records whose packed index is >= out_capacity are not written;
+ *                    out_counts is always complete, so the caller can size a second call.
+ *   d_workspace      pp_coco_workspace_size(n_img) bytes of device memory
+ * Two launches on `stream` (counts, then records).  Checked before any launch: NULL
+ * pointers (d_hswap may be NULL) and a misaligned `out` -> PP_EINVAL; K outside
+ * [1, PP_MAX_KP], max_per_image < 1, negative sizes or capacity < 1 -> PP_ESHAPE.
+ * pp_coco_keypoints_cpu / pp_coco_dets_cpu: the same on HOST pointers, on the calling
+ * thread, byte for byte (no workspace, no stream).
+ */
+#define PP_COCO_NAN 1
+#define PP_COCO_EMPTY 2
+typedef struct pp_coco_params {
+    double small_threshold;   /* EvalCoco.small_threshold   eval_coco.py:33 (0 = no filter) */
+    int32_t max_per_image;    /* EvalCoco.max_per_image     eval_coco.py:32 (20)            */
+    int32_t category_id;      /* Annotation.category_id     annotation.py:13 (1); poses     */
+} pp_coco_params;
+typedef struct pp_coco_det {
+    int64_t image_id;
+    double score;
+    double bbox[4];
+    int32_t category_id;
+    int32_t pad_;
+} pp_coco_det;
+int64_t pp_coco_record_size(int32_t K);
+size_t pp_coco_workspace_size(int32_t n_img);
+int pp_coco_keypoints(const pp_ann *d_anns, const int32_t *d_counts, int32_t n_img,
+                      int32_t capacity, int32_t K, const pp_inverse_meta *d_metas,
+                      const int64_t *d_image_ids, const int32_t *d_hswap,
+                      const pp_coco_params *params, void *out, int64_t out_capacity,
+                      int32_t *out_counts, int32_t *out_flags, void *d_workspace, void *stream);
+int pp_coco_dets(const pp_det *d_dets, const int32_t *d_counts, int32_t n_img, int32_t capacity,
+                 const pp_inverse_meta *d_metas, const int64_t *d_image_ids,
+                 const pp_coco_params *params, pp_coco_det *out, int64_t out_capacity,
+                 int32_t *out_counts, int32_t *out_flags, void *d_workspace, void *stream);
+int pp_coco_keypoints_cpu(const pp_ann *anns, const int32_t *counts, int32_t n_img,
+                          int32_t capacity, int32_t K, const pp_inverse_meta *metas,
+                          const int64_t *image_ids, const int32_t *hswap,
+                          const pp_coco_params *params, void *out, int64_t out_capacity,
+                          int32_t *out_counts, int32_t *out_flags);
+int pp_coco_dets_cpu(const pp_det *dets, const int32_t *counts, int32_t n_img, int32_t capacity,
+                     const pp_inverse_meta *metas, const int64_t *image_ids,
+                     const pp_coco_params *params, pp_coco_det *out, int64_t out_capacity,
+                     int32_t *out_counts, int32_t *out_flags);
+
+/*
  * Field ingestion: the raw output of a CompositeFieldFused head's conv (network/heads.py:
  * 406-455, eval mode) -> the decoder's field layout, as CifCafCollector /
  * CifdetCollector.forward (heads.py:65-88, 127-144) produce it: `quad` PixelShuffle(2)

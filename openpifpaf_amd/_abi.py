@@ -167,6 +167,30 @@ DET_DTYPE = np.dtype([('field', '<i4'), ('score', '<f4'), ('bbox', '<f4', (4,)),
 assert DET_DTYPE.itemsize == 32
 
 
+PP_COCO_NAN = 1
+PP_COCO_EMPTY = 2
+
+
+class CocoParams(ctypes.Structure):
+    """pp_coco_params: EvalCoco's small_threshold / max_per_image (eval_coco.py:32-33) and
+    the poses' category_id."""
+    _fields_ = [('small_threshold', ctypes.c_double), ('max_per_image', ctypes.c_int32),
+                ('category_id', ctypes.c_int32)]
+
+
+def coco_dtype(k):
+    """One COCO pose record of pp_coco_keypoints, pp_coco_record_size(K) = 56 + 24 K bytes."""
+    return np.dtype([('image_id', '<i8'), ('score', '<f8'), ('bbox', '<f8', (4,)),
+                     ('category_id', '<i4'), ('n_keypoints', '<i4'),
+                     ('keypoints', '<f8', (k, 3))])
+
+
+# pp_coco_det: one COCO detection record of pp_coco_dets
+COCO_DET_DTYPE = np.dtype([('image_id', '<i8'), ('score', '<f8'), ('bbox', '<f8', (4,)),
+                           ('category_id', '<i4'), ('pad_', '<i4')])
+assert COCO_DET_DTYPE.itemsize == 56 and coco_dtype(17).itemsize == 464
+
+
 class DetNms(ctypes.Structure):
     """pp_det_nms: nms.Detection class attributes (nms.py:60-65)."""
     _fields_ = [('suppression', ctypes.c_float), ('suppression_soft', ctypes.c_float),

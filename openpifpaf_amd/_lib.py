@@ -85,6 +85,17 @@ _SIGNATURES = {
     'pp_default_det_nms': ([_vp], None),
     'pp_annotations_inverse': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], ctypes.c_int),
     'pp_dets_inverse': ([_vp, _vp, _i32, _i32, _vp, _vp], ctypes.c_int),
+    # COCO prediction records (csrc/coco.hip) and their host twins (csrc/coco_cpu.hip)
+    'pp_coco_record_size': ([_i32], _i64),
+    'pp_coco_workspace_size': ([_i32], _sz),
+    'pp_coco_keypoints': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                           _vp, _vp], ctypes.c_int),
+    'pp_coco_dets': ([_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+                     ctypes.c_int),
+    'pp_coco_keypoints_cpu': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                               _vp], ctypes.c_int),
+    'pp_coco_dets_cpu': ([_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+                         ctypes.c_int),
     'pp_cifdet_hr': ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
     'pp_cifdet_seeds': ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp], ctypes.c_int),
     'pp_cifdet_hr_multi': ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp], ctypes.c_int),

@@ -253,6 +253,37 @@ class CifCaf(Generator):
             return None, None, HeadSet(fields, self.field_config)
         return self._decode_sharded(n, take, group, dst, local)
 
+    def coco_batch(self, cif_batch, caf_batch, metas, **params):
+        """(B, K, 5, H, W) + (B, C, 9, H, W) and one meta dict per image (with 'image_id')
+        -> the batch's eval_coco.CocoRecords: EvalCoco.from_predictions
+        (eval_coco.py:108-158) on the device behind the decode, without Annotation objects.
+        `params`: small_threshold, max_per_image, category_id."""
+        return self._coco(_device.to_device(cif_batch), _device.to_device(caf_batch), None, metas,
+                          params)
+
+    def coco_heads(self, heads, metas, **params):
+        """coco_batch from the model's head list (each (B, ...)) through the FieldConfig."""
+        if self.field_config.is_single_scale():
+            cif_i, caf_i, _ = self.field_config.single_scale()
+            return self.coco_batch(heads[cif_i], heads[caf_i], metas, **params)
+        used = set(self.field_config.cif_indices) | set(self.field_config.caf_indices)
+        head_set = HeadSet([_device.to_device(h) if i in used else None
+                            for i, h in enumerate(heads)], self.field_config)
+        return self._coco(None, None, head_set, metas, params)
+
+    def _coco(self, cif, caf, heads, metas, params):
+        from ...eval_coco import metas_device  # pylint: disable=import-outside-toplevel
+        if self.nms is not None and not self._device_nms():
+            raise TypeError('coco_batch needs the device NMS (nms.Keypoints or None): a host '
+                            'NMS object leaves no device records')
+        n = len(cif) if heads is None else heads.n
+        if len(metas) != n:
+            raise ValueError('{} metas for {} images'.format(len(metas), n))
+        b = engine().launch_checked(cif, caf, skeleton_array(self.skeleton), self.config(),
+                                    heads=heads)
+        d_metas, d_ids, d_swap = metas_device(metas, len(self.keypoints))
+        return engine().fetch_coco_async(b, d_metas, d_ids, hswap=d_swap, **params).result()
+
     def _decode_sharded(self, n, take, group, dst, local):
         import torch.distributed as dist  # pylint: disable=import-outside-toplevel
         rank, world = dist.get_rank(group), dist.get_world_size(group)

@@ -63,6 +63,34 @@ class CifDet(Generator):
         """det_batch (B, K, 7, H, W), or with several heads / min scales the list of the
         FieldConfig's heads (each (B, K, 7, H_m, W_m), cif_indices order) -> (pp_det
         records, per-image offsets)."""
+        out, counts = self.decode_device(det_batch, cap)
+        b = len(counts)
+        counts = counts.cpu().numpy().astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(counts)])
+        host = out.cpu().numpy()
+        recs = np.concatenate([host[i, :counts[i]].reshape(-1) for i in range(b)])
+        return np.frombuffer(recs.tobytes(), dtype=DET_DTYPE), offsets
+
+    def coco_batch(self, det_batch, metas, **params):
+        """decode_records' input and one meta dict per image (with 'image_id') -> the batch's
+        eval_coco.CocoRecords of detections: EvalCoco.from_predictions
+        (eval_coco.py:108-158) on the device behind the decode.  `params`: max_per_image."""
+        from ...eval_coco import coco_records, metas_device  # pylint: disable=import-outside-toplevel
+        out, counts = self.decode_device(det_batch)
+        if len(metas) != len(counts):
+            raise ValueError('{} metas for {} images'.format(len(metas), len(counts)))
+        d_metas, d_ids, _ = metas_device(metas, 0)
+        return coco_records(out, counts, d_metas, d_ids, det=True,
+                            k=params.pop('n_keypoints', 17), **params)
+
+    def coco_heads(self, heads, metas, **params):
+        """coco_batch from the model's head list (each (B, ...))."""
+        heads = self.head_fields(heads)
+        return self.coco_batch(heads[0] if self.single_head() else heads, metas, **params)
+
+    def decode_device(self, det_batch, cap=None):
+        """decode_records up to the device records: ((B, cap, record bytes) uint8, (B) int32
+        counts), complete (the capacity doubles until no image overflows)."""
         heads = [_device.to_device(t) for t in
                  (det_batch if isinstance(det_batch, (list, tuple)) else [det_batch])]
         for det in heads:
@@ -110,11 +138,7 @@ class CifDet(Generator):
             if cap >= k * cells:
                 raise PPError('CifDet: detection capacity overflow')
             cap = min(k * cells, 2 * cap)
-        counts = counts.cpu().numpy().astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
-        host = out.cpu().numpy()
-        recs = np.concatenate([host[i, :counts[i]].reshape(-1) for i in range(b)])
-        return np.frombuffer(recs.tobytes(), dtype=DET_DTYPE), offsets
+        return out, counts
 
     def annotations_from_records(self, recs, offsets):
         return [[AnnotationDet.from_record(r, self.categories)

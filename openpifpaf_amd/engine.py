@@ -334,6 +334,33 @@ class DecodeEngine:
         return p
 
     @staticmethod
+    def fetch_coco_async(b, metas, image_ids, *, hswap=None, small_threshold=0.0,
+                         max_per_image=20, category_id=1, capacity=0, stream=None):
+        """Enqueue the COCO prediction records (EvalCoco.from_predictions,
+        eval_coco.py:108-158) of the last decode into `b` and return an
+        eval_coco.PendingCoco; its result() waits and gives the batch's CocoRecords.
+
+        As fetch_async: on the engine's pack stream (or `stream`) after the decode, the
+        records written image after image straight into a pinned host block behind the
+        counts, the decode's status and the per-image flags, and packed again into a larger
+        block should the batch outgrow `capacity` records.  `metas` (device META_DTYPE
+        bytes), `image_ids` (device int64) and `hswap` (device int32 or None) as
+        eval_coco.metas_device builds them.  The decode's records are only read; result()
+        raises PPError when the decode set an overflow bit."""
+        from .eval_coco import coco_records_async  # pylint: disable=import-outside-toplevel
+        decoded = torch.cuda.Event()
+        decoded.record()
+        side = DecodeEngine._pack_stream(b.anns.device) if stream is None else stream
+        side.wait_event(decoded)
+        recs = b.anns.view(b.n, b.cap, ANN_DTYPE.itemsize)
+        p = coco_records_async(recs, b.counts, metas, image_ids, k=b.k, hswap=hswap,
+                               small_threshold=small_threshold, max_per_image=max_per_image,
+                               category_id=category_id, status=b.status, capacity=capacity,
+                               stream=side)
+        b._free[b._cur] = p.done_event
+        return p
+
+    @staticmethod
     def _pack(b, anns, counts, status, compact, device_out, est, after, stream=None):
         n = b.n
         dtype = ANN_DTYPE if compact is None else packed_dtype(*compact)
