@@ -90,7 +90,9 @@ __device__ __forceinline__ void flood_fill(const GrowArgs &g, GrowLDS &L) {  // 
 // set are unchanged by it (their frontier is empty) and are skipped, and images the seed
 // loop did not flag return at once.
 // (5 or 6 waves per SIMD via amdgpu_waves_per_eu: 21 / 46 spills, slower)
-template <bool CS>
+// NS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
+// directed edges.
+template <bool CS, int NS>
 __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
     __shared__ GrowLDS L;
     const int img = blockIdx.x;
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
         copy_ann(&L.a, &work[i]);
         uint32_t unfilled = 0;
         for (int j = 0; j < K; j++) unfilled |= (L.a.data[j][2] == 0.0f) ? (1u << j) : 0u;
-        grow<false, CS, GrowLDS>(g, L, img, 1, false);
+        grow<false, CS, NS, GrowLDS>(g, L, img, 1, false);
         bool any0 = false;
         for (int j = 0; j < K; j++) {
             float &v = L.a.data[j][2];
@@ -142,10 +144,12 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
 // force-complete, `ways` workgroups per image (they pull annotations from a per-image counter)
 int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s) {
     const dim3 grid(n_img, ways);
-    if (g.has_cs)
-        hipLaunchKernelGGL(complete_kernel<true>, grid, dim3(64), 0, s, g);
+    if (g.has_cs)  // (two-slot at every skeleton size, as in launch_seed_loop)
+        hipLaunchKernelGGL((complete_kernel<true, 2>), grid, dim3(64), 0, s, g);
+    else if (g.nd <= 64)
+        hipLaunchKernelGGL((complete_kernel<false, 1>), grid, dim3(64), 0, s, g);
     else
-        hipLaunchKernelGGL(complete_kernel<false>, grid, dim3(64), 0, s, g);
+        hipLaunchKernelGGL((complete_kernel<false, 2>), grid, dim3(64), 0, s, g);
     return check_launch("pp_decode_batch(force complete)");
 }
 

@@ -43,7 +43,9 @@ namespace pp {
 // measured slower (planted cfg3 323k vs 331k, uniform 12.4k vs 15.1k-15.7k images/s, round 4).
 // `abort` (a seed-loop helper's speculative grow): stop at the next pop once *abort is set
 // (wave 0 is done: the result would never be read)
-template <bool AHEAD, bool CS, typename LDS>
+// NS: the frontier's slots per lane (grow_frontier.hpp): 1 when g.nd <= 64, else 2; the
+// launchers pick the kernel instance.
+template <bool AHEAD, bool CS, int NS, typename LDS>
 __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set, bool reverse_match,
                                      const ColStage &cs = ColStage{}, int *abort = nullptr,
                                      float4 *pub = nullptr, uint32_t *pub_mask = nullptr) {
@@ -57,9 +59,9 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
         as = L.a.joint_scales[lane];
     }
     int nfr = L.a.n_frontier, ndec = L.a.n_decoding;
-    Frontier F;
+    Frontier<NS> F;
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
+    for (int r = 0; r < NS; r++) {
         const int d = lane + 64 * r;
         const bool ok = d < g.nd;
         F.st[r] = 0;
@@ -74,15 +76,16 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
         F.px[r] = F.py[r] = F.ps[r] = F.pv[r] = 0.0f;
     }
     const bool maxm = g.cfg.connection_method == 1;
-    SlotSets ss{};
-    if (AHEAD) ss = slot_sets(g, cs);
-    auto ahead = [&](const uint64_t added[2]) {
-        if (!AHEAD || !(added[0] | added[1])) return;
+    SlotSets<NS> ss{};
+    if (AHEAD) ss = slot_sets<NS>(g, cs);
+    auto ahead = [&](const uint64_t (&added)[NS]) {
+        const uint64_t a1 = NS == 2 ? added[NS - 1] : 0ull;
+        if (!AHEAD || !(added[0] | a1)) return;
         FSTAMP_BEGIN
         if (maxm)
-            eval_ahead<true>(g, F, img, cs, ss, added[0], added[1], ax, ay, av, as, L);
+            eval_ahead<true>(g, F, img, cs, ss, added[0], a1, ax, ay, av, as, L);
         else
-            eval_ahead<false>(g, F, img, cs, ss, added[0], added[1], ax, ay, av, as, L);
+            eval_ahead<false>(g, F, img, cs, ss, added[0], a1, ax, ay, av, as, L);
         FSTAMP_END(L, 1)
     };
     // `pub` (the seed loop): every joint the annotation holds, as (x, y, v, scale) in LDS as
@@ -96,7 +99,7 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
     for (int j = 0; j < K; j++) {  // seeding the frontier (cifcaf.py:288-291)
         const float vj = rl_f(av, j);
         if (vj == 0.0f) continue;
-        uint64_t added[2];
+        uint64_t added[NS];
         add_to_frontier<CS>(g, L, F, av, j, vj, nfr, added);
         ahead(added);
     }
@@ -150,7 +153,7 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
             const int sl = e.slot & 63, sr = e.slot >> 6;  // re-push into the edge's slot
             if (lane == sl) {
 #pragma unroll
-                for (int r = 0; r < 2; r++) {
+                for (int r = 0; r < NS; r++) {
                     if (r != sr) continue;
                     F.st[r] = 2;
                     F.neg[r] = e.neg;
@@ -188,7 +191,7 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
             }
         }
         ndec++;
-        uint64_t added[2];
+        uint64_t added[NS];
         {
             FSTAMP_BEGIN
             add_to_frontier<CS>(g, L, F, av, jti, got.v, nfr, added);

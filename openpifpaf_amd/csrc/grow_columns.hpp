@@ -77,16 +77,18 @@ __device__ __forceinline__ void flat_load_set(const float *__restrict__ cf, int6
 
 // per directed-edge slot (one per lane and half, like the Frontier): both directions' set
 // sizes and LDS offsets packed as (count << 16) | (offset + 1), and whether both are small
+template <int NS>
 struct SlotSets {
-    int f[2], b[2];
-    uint64_t small[2];
+    int f[NS], b[NS];
+    uint64_t small[NS];
 };
 
-__device__ __forceinline__ SlotSets slot_sets(const GrowArgs &g, const ColStage &cs) {
+template <int NS>
+__device__ __forceinline__ SlotSets<NS> slot_sets(const GrowArgs &g, const ColStage &cs) {
     const int lane = threadIdx.x & 63;
-    SlotSets t;
+    SlotSets<NS> t;
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
+    for (int r = 0; r < NS; r++) {
         const int d = lane + 64 * r;
         int f = 0, b = 0;
         bool small = false;
@@ -123,14 +125,19 @@ __device__ __forceinline__ void flat_query(const float v[kFlatPer][kColRows], in
 
 // the new entries `added` (slot masks, add_to_frontier) of a start joint: connection_value
 // with reverse_match (cifcaf.py:194-217) for those whose two column sets are small
-template <bool MAXM, typename LDS>
-__device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int img, const ColStage &cs,
-                                           const SlotSets &ss, uint64_t r0, uint64_t r1, float ax,
-                                           float ay, float av, float as, LDS &L) {
+// (r1: the slots from 64 on, always 0 with one slot per lane)
+template <bool MAXM, int NS, typename LDS>
+__device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier<NS> &F, int img,
+                                           const ColStage &cs, const SlotSets<NS> &ss, uint64_t r0,
+                                           uint64_t r1, float ax, float ay, float av, float as,
+                                           LDS &L) {
     const int lane = threadIdx.x & 63;
     const int64_t hw = g.col_cap;
     r0 &= ss.small[0];  // the others stay lazy
-    r1 &= ss.small[1];
+    if constexpr (NS == 2)
+        r1 &= ss.small[1];
+    else
+        r1 = 0;
     while (r0 | r1) {
         STAMP_T0(et);
         int sl[kAhead];
@@ -153,11 +160,11 @@ __device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int i
         for (int b = 0; b < kAhead; b++) {
             if (sl[b] < 0) continue;
             const int d = sl[b], l = d & 63;
-            const bool h = d >= 64;
-            const int pf = rl_i(h ? ss.f[1] : ss.f[0], l), pb = rl_i(h ? ss.b[1] : ss.b[0], l);
-            const int caf = rl_i(h ? F.scaf[1] : F.scaf[0], l);
-            const int df = rl_i(h ? F.sfwd[1] : F.sfwd[0], l) ? 1 : 0;
-            jj[b] = rl_i(h ? F.sj[1] : F.sj[0], l);
+            const bool h = NS == 2 && d >= 64;
+            const int pf = rl_i(PP_SLOT(ss.f, h), l), pb = rl_i(PP_SLOT(ss.b, h), l);
+            const int caf = rl_i(PP_SLOT(F.scaf, h), l);
+            const int df = rl_i(PP_SLOT(F.sfwd, h), l) ? 1 : 0;
+            jj[b] = rl_i(PP_SLOT(F.sj, h), l);
             nf[b] = pf >> 16;
             nb[b] = pb >> 16;
             flat_load_set(col_set(g, 0, img, caf, df), hw, nf[b], cs.lds, (pf & 0xFFFF) - 1, vf[b]);
@@ -188,13 +195,13 @@ __device__ __forceinline__ void eval_ahead(const GrowArgs &g, Frontier &F, int i
                 }
             }
             if (lane == (d & 63)) {
-                if (d < 64) {
+                if (NS == 1 || d < 64) {
                     F.pc[0] = 1;
                     F.px[0] = res[0];
                     F.py[0] = res[1];
                     F.ps[0] = res[2];
                     F.pv[0] = res[3];
-                } else {
+                } else if constexpr (NS == 2) {
                     F.pc[1] = 1;
                     F.px[1] = res[0];
                     F.py[1] = res[1];

@@ -7,18 +7,29 @@
 namespace pp {
 
 // ---------------------------------------------------------------------------------------
-// the frontier in registers: lane l holds directed-edge slots l and l + 64
+// the frontier in registers: lane l holds directed-edge slots l and, with NS == 2, l + 64
 // ---------------------------------------------------------------------------------------
+// NS slots per lane: 1 for a skeleton of at most 64 directed edges (COCO has 38), where the
+// second slot would always stay empty, else 2 (up to 128 directed edges).  The one-slot form
+// is the two-slot form with every `r == 1` term folded away: the same pops in the same
+// order, without slot 1's selects, its second ds_bpermute and ballot per add_to_frontier and
+// its 17 live registers.
+template <int NS>
 struct Frontier {
-    int st[2];         // 0 empty, 1 (-max_possible, None, j, k), 2 (-score, xysv, j, k)
-    float neg[2];
-    float x[2], y[2], s[2], v[2];
-    int added[2];      // in_frontier (cifcaf.py:249)
-    int sj[2], sk[2], scaf[2], sfwd[2];  // slot constants
+    int st[NS];         // 0 empty, 1 (-max_possible, None, j, k), 2 (-score, xysv, j, k)
+    float neg[NS];
+    float x[NS], y[NS], s[NS], v[NS];
+    int added[NS];      // in_frontier (cifcaf.py:249)
+    int sj[NS], sk[NS], scaf[NS], sfwd[NS];  // slot constants
     // connection_value of an unevaluated entry computed ahead of its pop (eval_ahead)
-    int pc[2];
-    float px[2], py[2], ps[2], pv[2];
+    int pc[NS];
+    float px[NS], py[NS], ps[NS], pv[NS];
 };
+
+// slot `w ? 1 : 0` of a per-slot array, as a select (not a[w]: a dynamic index sends the
+// frontier to scratch); with one slot there is nothing to select.  (A macro: through an
+// inlined function the two-slot kernels came out with 11 more VGPRs.)
+#define PP_SLOT(a, w) (NS == 2 ? ((w) ? (a)[NS - 1] : (a)[0]) : (a)[0])
 
 struct Entry {
     int slot, eval, j, k, caf, fwd, pc;
@@ -43,29 +54,32 @@ __device__ __forceinline__ bool entry_less(float na, int ea, float xa, float ya,
     return ka < kb;
 }
 
-__device__ __forceinline__ bool slot_less(const Frontier &F, int a, int b) {
+template <int NS>
+__device__ __forceinline__ bool slot_less(const Frontier<NS> &F, int a, int b) {
     return entry_less(F.neg[a], F.st[a] == 2, F.x[a], F.y[a], F.s[a], F.v[a], F.sj[a], F.sk[a],
                       F.neg[b], F.st[b] == 2, F.x[b], F.y[b], F.s[b], F.v[b], F.sj[b], F.sk[b]);
 }
 
 // PriorityQueue.get(): remove and return the smallest live entry (false when empty)
-__device__ __forceinline__ bool frontier_pop(Frontier &F, Entry &e) {
+template <int NS>
+__device__ __forceinline__ bool frontier_pop(Frontier<NS> &F, Entry &e) {
     const int lane = threadIdx.x & 63;
     int lb = -1;
     if (F.st[0]) lb = 0;
-    if (F.st[1] && (lb < 0 || slot_less(F, 1, 0))) lb = 1;
+    if constexpr (NS == 2)
+        if (F.st[1] && (lb < 0 || slot_less(F, 1, 0))) lb = 1;
     const uint64_t live = __ballot(lb >= 0);
     if (live == 0) return false;
-    const bool w1 = lb == 1;  // selects, not F.x[w]: a dynamic index sends F to scratch
-    const float myneg = lb >= 0 ? (w1 ? F.neg[1] : F.neg[0]) : INFINITY;
+    const bool w1 = lb == 1;
+    const float myneg = lb >= 0 ? PP_SLOT(F.neg, w1) : INFINITY;
     const float mn = wave_fmin(myneg);
     uint64_t cand = __ballot(lb >= 0 && myneg == mn);
     if (cand == 0) cand = live;  // only NaN scores left
     int win = __ffsll((unsigned long long)cand) - 1;
-    const float my_x = w1 ? F.x[1] : F.x[0], my_y = w1 ? F.y[1] : F.y[0];
-    const float my_s = w1 ? F.s[1] : F.s[0], my_v = w1 ? F.v[1] : F.v[0];
-    const int my_e = (w1 ? F.st[1] : F.st[0]) == 2, my_j = w1 ? F.sj[1] : F.sj[0];
-    const int my_k = w1 ? F.sk[1] : F.sk[0];
+    const float my_x = PP_SLOT(F.x, w1), my_y = PP_SLOT(F.y, w1);
+    const float my_s = PP_SLOT(F.s, w1), my_v = PP_SLOT(F.v, w1);
+    const int my_e = PP_SLOT(F.st, w1) == 2, my_j = PP_SLOT(F.sj, w1);
+    const int my_k = PP_SLOT(F.sk, w1);
     if (__popcll(cand) > 1) {  // exact score tie: full tuple comparison (rare)
         uint64_t rest = cand & (cand - 1);
         while (rest) {
@@ -78,7 +92,7 @@ __device__ __forceinline__ bool frontier_pop(Frontier &F, Entry &e) {
                 win = c;
         }
     }
-    const int wr = rl_i(w1 ? 1 : 0, win);
+    const int wr = NS == 2 ? rl_i(w1 ? 1 : 0, win) : 0;
     e.slot = win + 64 * wr;
     e.neg = rl_f(myneg, win);
     e.eval = rl_i(my_e, win);
@@ -88,31 +102,36 @@ __device__ __forceinline__ bool frontier_pop(Frontier &F, Entry &e) {
     e.v = rl_f(my_v, win);
     e.j = rl_i(my_j, win);
     e.k = rl_i(my_k, win);
-    e.caf = rl_i(wr ? F.scaf[1] : F.scaf[0], win);
-    e.fwd = rl_i(wr ? F.sfwd[1] : F.sfwd[0], win);
-    e.pc = rl_i(wr ? F.pc[1] : F.pc[0], win);
-    e.px = rl_f(wr ? F.px[1] : F.px[0], win);
-    e.py = rl_f(wr ? F.py[1] : F.py[0], win);
-    e.ps = rl_f(wr ? F.ps[1] : F.ps[0], win);
-    e.pv = rl_f(wr ? F.pv[1] : F.pv[0], win);
+    e.caf = rl_i(PP_SLOT(F.scaf, wr), win);
+    e.fwd = rl_i(PP_SLOT(F.sfwd, wr), win);
+    e.pc = rl_i(PP_SLOT(F.pc, wr), win);
+    e.px = rl_f(PP_SLOT(F.px, wr), win);
+    e.py = rl_f(PP_SLOT(F.py, wr), win);
+    e.ps = rl_f(PP_SLOT(F.ps, wr), win);
+    e.pv = rl_f(PP_SLOT(F.pv, wr), win);
     if (lane == win) {
-        if (wr)
-            F.st[1] = 0;
-        else
+        if constexpr (NS == 2) {
+            if (wr)
+                F.st[1] = 0;
+            else
+                F.st[0] = 0;
+        } else {
             F.st[0] = 0;
+        }
     }
     return true;
 }
 
 // add_to_frontier (cifcaf.py:251-263): the start joint's slots in dict order, one pass
-template <bool CS, typename LDS>
-__device__ __forceinline__ void add_to_frontier(const GrowArgs &g, LDS &L, Frontier &F, float av, int start,
-                                float start_v, int &nfr, uint64_t added[2]) {
+template <bool CS, int NS, typename LDS>
+__device__ __forceinline__ void add_to_frontier(const GrowArgs &g, LDS &L, Frontier<NS> &F, float av,
+                                                int start, float start_v, int &nfr,
+                                                uint64_t (&added)[NS]) {
     const int lane = threadIdx.x & 63;
     const int lo = g.j_off[start], hi = g.j_off[start + 1];
     const float neg = -sqrtf(start_v);
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
+    for (int r = 0; r < NS; r++) {
         const int d = lane + 64 * r;
         const float tv = __shfl(av, F.sk[r]);  // target joint's v (all lanes shuffle)
         const bool elig = d >= lo && d < hi && !(tv > 0.0f) && !F.added[r];

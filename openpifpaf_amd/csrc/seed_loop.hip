@@ -149,7 +149,10 @@ __device__ __noinline__ uint64_t spec_plan(SeedLoopShared &S, const pp_seed *see
 // overlapped step; 4 waves per SIMD (128 VGPRs, 532 spills): 1.37 ms.
 // Grid: n_img image workgroups, then n_ext * n_img external helper workgroups (helper
 // workgroup x of image i is block n_img * (1 + x) + i, on image i's XCD when n_img % 8 == 0).
-template <bool CS>
+// NS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
+// directed edges: seed_loop_kernel<false, 1> needs 154 VGPRs and no spills where the two-slot
+// instance sits at the 168 cap with 28 (tools/resource_usage.py).
+template <bool CS, int NS>
 __global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
 void seed_loop_kernel(GrowArgs g) {
     __shared__ SeedLDS Ls[kSeedWaves];
@@ -277,7 +280,7 @@ void seed_loop_kernel(GrowArgs g) {
             const int q = S.task_slot[wave];
             STAMP_T0(hg0);
             ann_from_seed(L, seeds[my], K, img);
-            grow<true, CS>(g, L, img, 0, true, cstage, &S.done, S.cache_j[q], &S.cache_pm[q]);
+            grow<true, CS, NS>(g, L, img, 0, true, cstage, &S.done, S.cache_j[q], &S.cache_pm[q]);
             STAMP_DO(if (lane == 0) {  // helper grows and their cycles (phase-1 slots 8 and 5)
                 L.fst[4] += 1;
                 L.fst[5] += STAMP_SINCE(hg0);
@@ -309,7 +312,7 @@ void seed_loop_kernel(GrowArgs g) {
         }
     } else {
         __builtin_amdgcn_s_setprio(3);  // the committer is the critical path: issue first
-        grow_initial<CS>(g, L, img, cstage, n_anns, [&](const pp_ann *a) {
+        grow_initial<CS, NS>(g, L, img, cstage, n_anns, [&](const pp_ann *a) {
             commit(a, lane < K ? a->data[lane][0] : 0.0f, lane < K ? a->data[lane][1] : 0.0f,
                    lane < K ? a->data[lane][2] : 0.0f, lane < K ? a->joint_scales[lane] : 0.0f);
         });
@@ -351,7 +354,7 @@ void seed_loop_kernel(GrowArgs g) {
             STAMP_DO(n_rounds++);
             STAMP(1);
             ann_from_seed(L, st, K, img);
-            grow<true, CS>(g, L, img, 0, true, cstage, nullptr, S.own_j, &S.own_pm);
+            grow<true, CS, NS>(g, L, img, 0, true, cstage, nullptr, S.own_j, &S.own_pm);
             STAMP(2);
             commit(&L.a, lane < K ? L.a.data[lane][0] : 0.0f, lane < K ? L.a.data[lane][1] : 0.0f,
                    lane < K ? L.a.data[lane][2] : 0.0f, lane < K ? L.a.joint_scales[lane] : 0.0f);
@@ -399,12 +402,15 @@ void seed_loop_kernel(GrowArgs g) {
 int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s) {
     const size_t dyn = kColLds * sizeof(float);
     // confidence_scales: their own kernel instances (the default ones carry no
-    // registers for them: complete_kernel stays at 128 VGPRs, 4 waves per SIMD)
+    // registers for them: complete_kernel stays at 128 VGPRs, 4 waves per SIMD); they keep
+    // the two-slot frontier at every skeleton size (fewer instances to compile)
     const dim3 blk(64 * kSeedWaves);
     if (g.has_cs)
-        hipLaunchKernelGGL(seed_loop_kernel<true>, dim3(n_img), blk, dyn, s, g);
+        hipLaunchKernelGGL((seed_loop_kernel<true, 2>), dim3(n_img), blk, dyn, s, g);
+    else if (g.nd <= 64)
+        hipLaunchKernelGGL((seed_loop_kernel<false, 1>), dim3(n_img), blk, dyn, s, g);
     else
-        hipLaunchKernelGGL(seed_loop_kernel<false>, dim3(n_img), blk, dyn, s, g);
+        hipLaunchKernelGGL((seed_loop_kernel<false, 2>), dim3(n_img), blk, dyn, s, g);
     return check_launch("pp_decode_batch(seed loop)");
 }
 

@@ -306,7 +306,7 @@ __device__ __forceinline__ int next_free_seed(int &s, int n_seeds, const SeedOcc
 // all its set joints (its decoding / frontier orders are appended to), then committed
 // (appended and marked occupied, `commit(record)`), in order, before any seed is looked
 // at.  Wave 0.
-template <bool CS, typename Commit>
+template <bool CS, int NS, typename Commit>
 __device__ __forceinline__ void grow_initial(const GrowArgs &g, SeedLDS &L, int img,
                                              const ColStage &cstage, const int &n_anns,
                                              Commit commit) {
@@ -323,7 +323,7 @@ __device__ __forceinline__ void grow_initial(const GrowArgs &g, SeedLDS &L, int 
             L.a.n_keypoints = g.K;
         }
         wave_sync();
-        grow<true, CS>(g, L, img, 0, true, cstage);
+        grow<true, CS, NS>(g, L, img, 0, true, cstage);
         commit(&L.a);
     }
 }

@@ -202,7 +202,9 @@ __device__ __forceinline__ void ext_refresh(SeedLoopSharedX &S, float *s_cols, c
 // seed_loop_kernel's loop with external helpers (n_ext > 0).  A separate kernel: the
 // big-batch one (seed_loop.hip) carries none of the hand-off state, whose registers cost it
 // 4% per planted cfg3 step when merged into it (spills inside the grow).
-template <bool CS>
+// FS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
+// directed edges.
+template <bool CS, int FS>
 __global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
 void seed_loop_ext_kernel(GrowArgs g) {
     constexpr int NS = kCacheSlots;
@@ -313,7 +315,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
                 my = (int)(v >> 32);
             }
             ann_from_seed(L, seeds[my], K, img);
-            grow<true, CS>(g, L, img, 0, true, cstage, external ? nullptr : &S.done);
+            grow<true, CS, FS>(g, L, img, 0, true, cstage, external ? nullptr : &S.done);
             if (!external && lds_acquire(&S.done)) break;  // nobody reads the cache any more
             if (external) {
                 publish_ann(&xrec[q], &L.a);
@@ -342,7 +344,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
         }
     } else {
         __builtin_amdgcn_s_setprio(3);  // the committer is the critical path: issue first
-        grow_initial<CS>(g, L, img, cstage, n_anns, [&](const pp_ann *a) {
+        grow_initial<CS, FS>(g, L, img, cstage, n_anns, [&](const pp_ann *a) {
             commit(a, false, lane < K ? a->data[lane][0] : 0.0f,
                    lane < K ? a->data[lane][1] : 0.0f, lane < K ? a->data[lane][2] : 0.0f,
                    lane < K ? a->joint_scales[lane] : 0.0f);
@@ -563,7 +565,7 @@ void seed_loop_ext_kernel(GrowArgs g) {
             STAMP_DO(n_rounds++);
             STAMP(1);
             ann_from_seed(L, st, K, img);
-            grow<true, CS>(g, L, img, 0, true, cstage);
+            grow<true, CS, FS>(g, L, img, 0, true, cstage);
             STAMP(2);
             commit(&L.a, false, lane < K ? L.a.data[lane][0] : 0.0f,
                    lane < K ? L.a.data[lane][1] : 0.0f, lane < K ? L.a.data[lane][2] : 0.0f,
@@ -599,10 +601,12 @@ int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s) {
     // g.xext is zero: the workspace's zero region, which every external-helper seed
     // loop leaves zero (ext_exit)
     const dim3 grid(n_img * (1 + g.n_ext)), blk(64 * kSeedWaves);
-    if (g.has_cs)
-        hipLaunchKernelGGL(seed_loop_ext_kernel<true>, grid, blk, kExtDynLds, s, g);
+    if (g.has_cs)  // (two-slot at every skeleton size, as in launch_seed_loop)
+        hipLaunchKernelGGL((seed_loop_ext_kernel<true, 2>), grid, blk, kExtDynLds, s, g);
+    else if (g.nd <= 64)
+        hipLaunchKernelGGL((seed_loop_ext_kernel<false, 1>), grid, blk, kExtDynLds, s, g);
     else
-        hipLaunchKernelGGL(seed_loop_ext_kernel<false>, grid, blk, kExtDynLds, s, g);
+        hipLaunchKernelGGL((seed_loop_ext_kernel<false, 2>), grid, blk, kExtDynLds, s, g);
     return check_launch("pp_decode_batch(seed loop)");
 }
 
