@@ -693,6 +693,49 @@ size_t pp_decode_workspace_zero_offset(int32_t n_img, int32_t K, int32_t C, int3
                                        int32_t W, const pp_config *cfg, int32_t ann_capacity);
 
 /* ---------------------------------------------------------------------------------
+ * Ragged batches: images of different field sizes decoded in one batch.
+ *
+ * The images share a container: fields (n_img, K, 5, H, W) and (n_img, C, 9, H, W) with
+ * (H, W) at least every image's own (h_i, w_i), image i in the top-left h_i x w_i corner
+ * of its planes, and an (n_img, 2) int32 table of the (h_i, w_i).  The result is defined
+ * as that of decoding every image alone at its own size (pp_decode_ragged_cpu is that
+ * definition); zero-padding to a common size and pp_decode_batch give other annotations,
+ * because the reference's scalar_values bounds, its splat box clip and its occupancy grid
+ * follow the image's own CifHr size.  Everything else (workspace, capacities, outputs,
+ * status bits, stage mask) is pp_decode_stages' at the container's (H, W).
+ *
+ * pp_fields_pack_ragged builds one container: `fields` is a HOST array of n_img device
+ * pointers, image i's contiguous float32 (n_fields, channels, h_i, w_i), and `extents` the
+ * HOST (n_img, 2) table.  Both are copied into d_tables (pp_ragged_tables_size(n_img)
+ * bytes, 8-byte aligned) on the stream, pointers first; afterwards the device extent table
+ * pp_decode_ragged takes is at d_tables + pp_ragged_extents_offset(n_img).  Pageable host
+ * tables are consumed before the call returns, pinned ones when the stream reaches the copy.
+ * Every element of d_container (n_img, n_fields, channels, H, W) is written once: the
+ * image's value inside its extent, 0 outside, in 16-byte stores over each plane's 16-byte
+ * aligned interior (d_container needs 4-byte alignment only).  PP_ESHAPE: an extent <= 0 or
+ * larger than the container.
+ *
+ * pp_decode_ragged: single-scale.  d_extents is the device table, `extents` the same
+ * table on the host (argument checks only, read before the call returns).  Precondition:
+ * the confidence channel (channel 0) of every cell outside its image's extent is 0, as the
+ * packer leaves it.  PP_ESHAPE: an extent <= 0 or larger than the container.  PP_EINVAL: a
+ * negative cif_threshold, seed_threshold, caf_threshold or complete_caf_threshold (cells
+ * outside an extent must pass no `c > threshold`), or d_cifhr != NULL (a dense map of a
+ * ragged batch has no defined layout yet; the argument is kept for the signature's sake).
+ * --------------------------------------------------------------------------------- */
+size_t pp_ragged_tables_size(int32_t n_img);
+size_t pp_ragged_extents_offset(int32_t n_img);
+int pp_fields_pack_ragged(const float *const *fields, const int32_t *extents, int32_t n_img,
+                          int32_t n_fields, int32_t channels, int32_t H, int32_t W,
+                          float *d_container, void *d_tables, size_t tables_bytes, void *stream);
+int pp_decode_ragged(const float *d_cif, const float *d_caf, int32_t n_img, int32_t K,
+                     int32_t C, int32_t H, int32_t W, const int32_t *d_extents,
+                     const int32_t *extents, const int32_t *skeleton, const pp_config *cfg,
+                     float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
+                     int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                     uint32_t stages, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * openpifpaf.functional primitives (functional.pyx).  `field` arguments are
  * (h, w) float32 with row pitch `pitch` (elements).  Point lists are length-n device
  * arrays.  All are bit-exact restatements run as HIP kernels.
@@ -876,6 +919,17 @@ int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32
                         int32_t H, int32_t W, const int32_t *skeleton, const pp_config *cfg,
                         pp_ann *anns, int32_t ann_capacity, int32_t *counts, int32_t *status,
                         int32_t n_threads);
+
+/*
+ * Host twin of pp_decode_ragged and the definition of a ragged decode: image i is the
+ * extents[i] = (h_i, w_i) top-left crop of its container planes, decoded by
+ * pp_decode_batch_cpu's per-image decode at that size.  Same argument checks as
+ * pp_decode_ragged (extents on the host).
+ */
+int pp_decode_ragged_cpu(const float *cif, const float *caf, int32_t n_img, int32_t K, int32_t C,
+                         int32_t H, int32_t W, const int32_t *extents, const int32_t *skeleton,
+                         const pp_config *cfg, pp_ann *anns, int32_t ann_capacity,
+                         int32_t *counts, int32_t *status, int32_t n_threads);
 
 #ifdef __cplusplus
 }

@@ -155,6 +155,15 @@ _SIGNATURES = {
     # host twin of the whole decode (csrc/decode_cpu.hip)
     'pp_decode_batch_cpu': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                              _vp, _i32], ctypes.c_int),
+    # ragged batches (csrc/ragged.hip, decode.hip) and their host twin
+    'pp_ragged_tables_size': ([_i32], _sz),
+    'pp_ragged_extents_offset': ([_i32], _sz),
+    'pp_fields_pack_ragged': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp],
+                              ctypes.c_int),
+    'pp_decode_ragged': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                          _i32, _vp, _vp, _vp, _sz, _u32, _vp], ctypes.c_int),
+    'pp_decode_ragged_cpu': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
+                              _vp, _vp, _i32], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -92,8 +92,9 @@ __device__ __forceinline__ void flood_fill(const GrowArgs &g, GrowLDS &L) {  // 
 // (5 or 6 waves per SIMD via amdgpu_waves_per_eu: 21 / 46 spills, slower)
 // NS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
 // directed edges.
+// `ext` (hr_dims): NULL, or the images' own field sizes (complete_ragged_kernel).
 template <bool CS, int NS>
-__global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
+__device__ __forceinline__ void complete_body(const GrowArgs &g, const int32_t *ext) {
     __shared__ GrowLDS L;
     const int img = blockIdx.x;
     const int K = g.K;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
         copy_ann(&L.a, &work[i]);
         uint32_t unfilled = 0;
         for (int j = 0; j < K; j++) unfilled |= (L.a.data[j][2] == 0.0f) ? (1u << j) : 0u;
-        grow<false, CS, NS, GrowLDS>(g, L, img, 1, false);
+        grow<false, CS, NS, GrowLDS>(g, L, img, 1, false, ColStage{}, nullptr, nullptr, nullptr, ext);
         bool any0 = false;
         for (int j = 0; j < K; j++) {
             float &v = L.a.data[j][2];
@@ -138,12 +139,31 @@ __global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
     if (lane == 0 && L.status) atomicOr(&g.status[img], L.status);
 }
 
+template <bool CS, int NS>
+__global__ __launch_bounds__(64) void complete_kernel(GrowArgs g) {
+    complete_body<CS, NS>(g, nullptr);
+}
+
+template <bool CS, int NS>
+__global__ __launch_bounds__(64) void complete_ragged_kernel(GrowArgs g, const int32_t *ext) {
+    complete_body<CS, NS>(g, ext);
+}
+
 // ---------------------------------------------------------------------------------------
 // host: the kernel's launcher (decode.hip has the rest of the host side)
 // ---------------------------------------------------------------------------------------
 // force-complete, `ways` workgroups per image (they pull annotations from a per-image counter)
-int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s) {
+int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s, const int32_t *ext) {
     const dim3 grid(n_img, ways);
+    if (ext) {  // a ragged batch: the same instances over the extent table
+        if (g.has_cs)
+            hipLaunchKernelGGL((complete_ragged_kernel<true, 2>), grid, dim3(64), 0, s, g, ext);
+        else if (g.nd <= 64)
+            hipLaunchKernelGGL((complete_ragged_kernel<false, 1>), grid, dim3(64), 0, s, g, ext);
+        else
+            hipLaunchKernelGGL((complete_ragged_kernel<false, 2>), grid, dim3(64), 0, s, g, ext);
+        return check_launch("pp_decode_ragged(force complete)");
+    }
     if (g.has_cs)  // (two-slot at every skeleton size, as in launch_seed_loop)
         hipLaunchKernelGGL((complete_kernel<true, 2>), grid, dim3(64), 0, s, g);
     else if (g.nd <= 64)

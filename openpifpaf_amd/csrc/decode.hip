@@ -15,18 +15,20 @@ namespace pp {
 
 int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_config *cfg,
                  pp_seed *seeds, int cap, int *counts, void *scratch, hipStream_t s,
-                 bool emitted);
+                 bool emitted, const int32_t *ext);
 size_t seeds_scratch_size(int n_img, int cap);
 int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C,
                         const int32_t *skeleton, const pp_config *cfg, float th, float *cols,
-                        int *offs, const int *gate, bool index_only, hipStream_t s);
+                        int *offs, const int *gate, bool index_only, hipStream_t s,
+                        const int32_t *ext);
 void caf_bucket_grid(int H, int W, int stride, int *bw, int *bh, int *nb, float *inv_e);
 
 // the decoder's kernels, each launched from the file that defines it (seed_loop.hip,
 // seed_loop_ext.hip, complete.hip, nms.hip)
-int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s);
-int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s);
-int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s);
+// (ext: NULL, or a ragged batch's extent table, hr_dims)
+int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s, const int32_t *ext);
+int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s, const int32_t *ext);
+int launch_complete(const GrowArgs &g, int n_img, int ways, hipStream_t s, const int32_t *ext);
 int launch_nms(const GrowArgs &g, int n_img, bool wide, bool bitmap, hipStream_t s);
 
 struct DecodeLayout {
@@ -223,6 +225,8 @@ struct DecodeInit {
     const int32_t *counts = nullptr;
     int32_t cap = 0;
     int32_t *out_index = nullptr;
+    // pp_decode_ragged: the images' own field sizes, device (n_img, 2) (hr_dims)
+    const int32_t *extents = nullptr;
 };
 
 static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
@@ -255,6 +259,7 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
                                "more per side)");
     char *ws = (char *)d_workspace;
     hipStream_t s = (hipStream_t)stream;
+    const int32_t *ext = init.extents;
     // the caller's d_cifhr gets the dense map; otherwise the decoder keeps the block-sparse
     // scratch map, written only where splat boxes land
     float *hr_base = d_cifhr ? d_cifhr : (float *)(ws + d.off_cifhr);
@@ -279,7 +284,7 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
             hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
             return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
         rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                 cols[1], offs[1], nullptr, true, side->stream);
+                                 cols[1], offs[1], nullptr, true, side->stream, ext);
         if (rc) {
             (void)hipEventRecord(side->join, side->stream);
             (void)hipStreamWaitEvent(s, side->join, 0);
@@ -297,7 +302,7 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
             const SeedSink sink = seed_sink(n_img, K, cfg, d.seed_cap, ws + d.off_seed_ws);
             rc = cifhr_sparse_launch(h, n_img, K, cfg, hr_base, (float *)(ws + d.off_hr_aux),
                                      hr_masks, ws + d.off_cifhr_ws, d.cifhr_ws_bytes, s,
-                                     "pp_decode_batch(cifhr)", fused_seeds ? &sink : nullptr);
+                                     "pp_decode_batch(cifhr)", fused_seeds ? &sink : nullptr, ext);
         }
         if (rc) return rc;
     }
@@ -314,14 +319,14 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
             hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
             return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
         rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold, cols[0],
-                                 offs[0], nullptr, false, side->stream);
+                                 offs[0], nullptr, false, side->stream, ext);
         if (!rc && early_b)
             rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
                                      cfg->complete_caf_threshold, cols[1], offs[1], nullptr, true,
-                                     side->stream);
+                                     side->stream, ext);
         if (!rc)
             rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds);
+                              ws + d.off_seed_ws, s, fused_seeds, ext);
         // join even after a failed launch, so the caller's stream never runs ahead
         if (hipEventRecord(side->join, side->stream) != hipSuccess ||
             hipStreamWaitEvent(s, side->join, 0) != hipSuccess)
@@ -330,16 +335,16 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
     } else {
         if (stages & 2u) {
             rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds);
+                              ws + d.off_seed_ws, s, fused_seeds, ext);
             if (rc) return rc;
         }
         if (stages & 4u) {  // CafScored at caf_threshold; the force-complete set is lazy
             rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold,
-                                     cols[0], offs[0], nullptr, false, s);
+                                     cols[0], offs[0], nullptr, false, s, ext);
             if (!rc && early_b)
                 rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
                                          cfg->complete_caf_threshold, cols[1], offs[1], nullptr,
-                                         true, s);
+                                         true, s, ext);
             if (rc) return rc;
         }
     }
@@ -446,7 +451,7 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
         const bool run_rest = !(stages & PP_STAGE_SEED_LOOP_ONLY);
         if (!(stages & PP_STAGE_AFTER_SEED_LOOP)) {
             // external helper workgroups (images fewer than CUs) have a kernel of their own
-            rc = g.n_ext > 0 ? launch_seed_loop_ext(g, n_img, s) : launch_seed_loop(g, n_img, s);
+            rc = g.n_ext > 0 ? launch_seed_loop_ext(g, n_img, s, ext) : launch_seed_loop(g, n_img, s, ext);
             if (rc) return rc;
         }
         // PP_STAGE_COMPLETE_ONLY / PP_STAGE_NMS_ONLY split the rest once more
@@ -455,11 +460,11 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
         if (run_complete && cfg->force_complete && !(stages & PP_STAGE_COMPLETE_SETS_EARLY)) {
             // complete_annotations' CafScored(score_th=0.0001) only where phase 1 left work
             rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                     cols[1], offs[1], g.need_complete, true, s);
+                                     cols[1], offs[1], g.need_complete, true, s, ext);
             if (rc) return rc;
         }
         if (run_complete && cfg->force_complete) {
-            rc = launch_complete(g, n_img, complete_ways(stages), s);
+            rc = launch_complete(g, n_img, complete_ways(stages), s, ext);
             if (rc) return rc;
         }
         if (run_nms)
@@ -509,6 +514,33 @@ int pp_decode_stages(const float *d_cif, const float *d_caf, int32_t n_img, int3
     return decode_heads(single_head(d_cif, d_caf, H, W, cfg->stride), n_img, K, C, skeleton, cfg,
                         d_cifhr, d_anns, ann_capacity, d_counts, d_status, d_workspace,
                         workspace_bytes, stages, stream);
+}
+
+int pp_decode_ragged(const float *d_cif, const float *d_caf, int32_t n_img, int32_t K, int32_t C,
+                     int32_t H, int32_t W, const int32_t *d_extents, const int32_t *extents,
+                     const int32_t *skeleton, const pp_config *cfg, float *d_cifhr, pp_ann *d_anns,
+                     int32_t ann_capacity, int32_t *d_counts, int32_t *d_status, void *d_workspace,
+                     size_t workspace_bytes, uint32_t stages, void *stream) {
+    if (!d_cif || !d_caf || !cfg || !d_extents || !extents)
+        return fail(PP_EINVAL, "pp_decode_ragged: NULL argument");
+    if (d_cifhr)
+        return fail(PP_EINVAL, "pp_decode_ragged: the dense CifHr map of a ragged batch has no "
+                               "layout (d_cifhr must be NULL)");
+    if (H <= 0 || W <= 0 || cfg->stride <= 0) return fail(PP_ESHAPE, "pp_decode_ragged: bad shape");
+    // cells outside an extent hold confidence 0 and every threshold compare is c > th: they
+    // are candidates of nothing as long as no threshold is negative
+    if (cfg->cif_threshold < 0.0f || cfg->seed_threshold < 0.0f || cfg->caf_threshold < 0.0f ||
+        cfg->complete_caf_threshold < 0.0f)
+        return fail(PP_EINVAL, "pp_decode_ragged: a ragged batch needs thresholds >= 0");
+    for (int i = 0; i < n_img; i++)
+        if (extents[2 * i] <= 0 || extents[2 * i] > H || extents[2 * i + 1] <= 0 ||
+            extents[2 * i + 1] > W)
+            return fail(PP_ESHAPE, "pp_decode_ragged: extent outside the container");
+    DecodeInit init;
+    init.extents = d_extents;
+    return decode_heads(single_head(d_cif, d_caf, H, W, cfg->stride), n_img, K, C, skeleton, cfg,
+                        nullptr, d_anns, ann_capacity, d_counts, d_status, d_workspace,
+                        workspace_bytes, stages, stream, init);
 }
 
 int pp_decode_multi(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs, int32_t n_img,

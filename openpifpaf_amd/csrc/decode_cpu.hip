@@ -490,22 +490,32 @@ int decode_image(const float *cif, const float *caf, int K, int C, int H, int W,
 
 }  // namespace
 
-extern "C" {
-
-int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32_t K, int32_t C,
-                        int32_t H, int32_t W, const int32_t *skeleton, const pp_config *cfg,
-                        pp_ann *anns, int32_t ann_capacity, int32_t *counts, int32_t *status,
-                        int32_t n_threads) {
+// `extents` (pp_decode_ragged_cpu; NULL: every image is H x W): image i is the h_i x w_i
+// top-left crop of its container planes, decoded as a batch of its own would be
+static int decode_batch_host(const char *who, const float *cif, const float *caf, int32_t n_img,
+                             int32_t K, int32_t C, int32_t H, int32_t W, const int32_t *extents,
+                             const int32_t *skeleton, const pp_config *cfg, pp_ann *anns,
+                             int32_t ann_capacity, int32_t *counts, int32_t *status,
+                             int32_t n_threads) {
     if (!cif || !caf || !skeleton || !cfg || !anns || !counts || !status)
-        return pp::fail(PP_EINVAL, "pp_decode_batch_cpu: NULL argument");
+        return pp::fail(PP_EINVAL, std::string(who) + ": NULL argument");
     if (n_img < 0 || K <= 0 || K > PP_MAX_KP || C <= 0 || C > PP_MAX_EDGES || H <= 0 || W <= 0 ||
         ann_capacity <= 0 || cfg->stride <= 0 || cfg->occupancy_reduction <= 0)
-        return pp::fail(PP_ESHAPE, "pp_decode_batch_cpu: shape outside the supported envelope");
+        return pp::fail(PP_ESHAPE, std::string(who) + ": shape outside the supported envelope");
     if (cfg->connection_method != 0 && cfg->connection_method != 1)
         return pp::fail(PP_EINVAL, "connection method not known");
     for (int i = 0; i < 2 * C; i++)
         if (skeleton[i] < 1 || skeleton[i] > K)
-            return pp::fail(PP_EINVAL, "pp_decode_batch_cpu: skeleton joint index out of 1..K");
+            return pp::fail(PP_EINVAL, std::string(who) + ": skeleton joint index out of 1..K");
+    if (extents) {
+        if (cfg->cif_threshold < 0.0f || cfg->seed_threshold < 0.0f || cfg->caf_threshold < 0.0f ||
+            cfg->complete_caf_threshold < 0.0f)
+            return pp::fail(PP_EINVAL, std::string(who) + ": a ragged batch needs thresholds >= 0");
+        for (int i = 0; i < n_img; i++)
+            if (extents[2 * i] <= 0 || extents[2 * i] > H || extents[2 * i + 1] <= 0 ||
+                extents[2 * i + 1] > W)
+                return pp::fail(PP_ESHAPE, std::string(who) + ": extent outside the container");
+    }
     if (n_img == 0) return PP_OK;
     const BySource bs(skeleton, C);
     const int64_t hw = (int64_t)H * W;
@@ -515,11 +525,28 @@ int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32
     std::atomic<int> err{PP_OK};
     auto worker = [&]() {
         Scratch S;
+        std::vector<float> crop_cif, crop_caf;  // a ragged image's own contiguous fields
         for (;;) {
             const int img = next.fetch_add(1);
             if (img >= n_img || err.load() != PP_OK) return;
-            const int rc = decode_image(cif + (int64_t)img * K * 5 * hw, caf + (int64_t)img * C * 9 * hw,
-                                        K, C, H, W, skeleton, *cfg, bs,
+            const float *icif = cif + (int64_t)img * K * 5 * hw, *icaf = caf + (int64_t)img * C * 9 * hw;
+            int h = H, w = W;
+            if (extents) {
+                h = extents[2 * img];
+                w = extents[2 * img + 1];
+                auto crop = [&](const float *src, int64_t planes, std::vector<float> &dst) {
+                    dst.resize((size_t)(planes * h * w));
+                    for (int64_t p = 0; p < planes; p++)
+                        for (int y = 0; y < h; y++)
+                            std::memcpy(&dst[(size_t)((p * h + y) * w)], src + p * hw + (int64_t)y * W,
+                                        (size_t)w * sizeof(float));
+                };
+                crop(icif, (int64_t)K * 5, crop_cif);
+                crop(icaf, (int64_t)C * 9, crop_caf);
+                icif = crop_cif.data();
+                icaf = crop_caf.data();
+            }
+            const int rc = decode_image(icif, icaf, K, C, h, w, skeleton, *cfg, bs,
                                         anns + (int64_t)img * ann_capacity, ann_capacity,
                                         counts + img, status + img, S, img);
             if (rc != PP_OK) err.store(rc);
@@ -533,6 +560,25 @@ int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32
         for (auto &t : pool) t.join();
     }
     return err.load();
+}
+
+extern "C" {
+
+int pp_decode_batch_cpu(const float *cif, const float *caf, int32_t n_img, int32_t K, int32_t C,
+                        int32_t H, int32_t W, const int32_t *skeleton, const pp_config *cfg,
+                        pp_ann *anns, int32_t ann_capacity, int32_t *counts, int32_t *status,
+                        int32_t n_threads) {
+    return decode_batch_host("pp_decode_batch_cpu", cif, caf, n_img, K, C, H, W, nullptr, skeleton,
+                             cfg, anns, ann_capacity, counts, status, n_threads);
+}
+
+int pp_decode_ragged_cpu(const float *cif, const float *caf, int32_t n_img, int32_t K, int32_t C,
+                         int32_t H, int32_t W, const int32_t *extents, const int32_t *skeleton,
+                         const pp_config *cfg, pp_ann *anns, int32_t ann_capacity, int32_t *counts,
+                         int32_t *status, int32_t n_threads) {
+    if (!extents) return pp::fail(PP_EINVAL, "pp_decode_ragged_cpu: NULL argument");
+    return decode_batch_host("pp_decode_ragged_cpu", cif, caf, n_img, K, C, H, W, extents, skeleton,
+                             cfg, anns, ann_capacity, counts, status, n_threads);
 }
 
 }  // extern "C"

@@ -48,7 +48,8 @@ namespace pp {
 template <bool AHEAD, bool CS, int NS, typename LDS>
 __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set, bool reverse_match,
                                      const ColStage &cs = ColStage{}, int *abort = nullptr,
-                                     float4 *pub = nullptr, uint32_t *pub_mask = nullptr) {
+                                     float4 *pub = nullptr, uint32_t *pub_mask = nullptr,
+                                     const int32_t *ext = nullptr) {
     const int lane = threadIdx.x & 63;
     const int K = g.K;
     float ax = 0.0f, ay = 0.0f, av = 0.0f, as = 0.0f;
@@ -134,7 +135,7 @@ __device__ __forceinline__ void grow(const GrowArgs &g, LDS &L, int img, int set
                 STAMP_DO(if (lane == 0) L.fst[3] += 1);
                 FSTAMP_BEGIN
                 connection_value(g, img, set, e.caf, e.fwd, rl_f(ax, e.j), rl_f(ay, e.j),
-                                 rl_f(av, e.j), rl_f(as, e.j), reverse_match, nx);
+                                 rl_f(av, e.j), rl_f(as, e.j), reverse_match, nx, ext);
                 FSTAMP_END(L, 1)
             }
             if (nx[3] == 0.0f) continue;

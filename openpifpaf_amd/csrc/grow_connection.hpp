@@ -194,6 +194,7 @@ struct RawSet {
     int64_t fld;         // image * C + CAF field
     int64_t hrt;         // CifHr plane of the direction's target joint (rescore), or -1
     int src, tgt, tsc;   // raw rows of source x, target x, target scale (y = x + 1)
+    HrDims dm;           // the image's own CifHr size (hr_dims)
 };
 
 template <bool MAXM>
@@ -217,7 +218,7 @@ __device__ __forceinline__ void consider_raw(const GrowArgs &g, const RawSet &r,
     const float tc = caf9[r.tsc * hw + cell] * stride;
     if (c1 < q.lo_x || c1 > q.hi_x || c2 < q.lo_y || c2 > q.hi_y) return;
     float c0 = c;
-    if (r.hrt >= 0) c0 = c * (g.cif_floor + g.one_minus_floor * g.hr.at(r.hrt, tx, ty, 0.0f));
+    if (r.hrt >= 0) c0 = c * (g.cif_floor + g.one_minus_floor * g.hr.at(r.hrt, tx, ty, 0.0f, r.dm.hh, r.dm.ww));
     if (!(c0 > g.th_b)) return;
     const float dx = q.x - c1, dy = q.y - c2;
     const float dd = sqrtf(dx * dx + dy * dy);
@@ -359,8 +360,10 @@ __device__ __forceinline__ const float *col_set(const GrowArgs &g, int set, int 
 
 // set B of (image, CAF, direction): dir 1 forward (x1, y1) -> (x2, y2, s2), rescored at
 // joint j2; dir 0 backward (x2, y2) -> (x1, y1, s1), rescored at j1 (caf_scored.py:58-81)
-__device__ __forceinline__ RawSet raw_set(const GrowArgs &g, int img, int caf_i, int dir) {
+__device__ __forceinline__ RawSet raw_set(const GrowArgs &g, int img, int caf_i, int dir,
+                                          const int32_t *ext) {
     RawSet r;
+    r.dm = hr_dims(ext, img, g.heads.cstride[0], g.hr.hh, g.hr.ww);
     const float *cs = col_set(g, 1, img, caf_i, dir);
     const bool i16 = g.col_cap <= kSetBIdx16Max;  // caf_bucketed_kernel<true, true>
     r.idx = i16 ? nullptr : reinterpret_cast<const int *>(cs);
@@ -382,7 +385,7 @@ __device__ __forceinline__ const int *col_offs(const GrowArgs &g, int set, int i
 // cifcaf.py:194-217 for start joint (jx, jy, jv, js) along CAF caf_i in direction fwd
 __device__ __forceinline__ void connection_value(const GrowArgs &g, int img, int set, int caf_i, int fwd,
                                  float jx, float jy, float jv, float js, bool reverse_match,
-                                 float out[4]) {
+                                 float out[4], const int32_t *ext = nullptr) {
     const int df = fwd ? 1 : 0, db = fwd ? 0 : 1;
     const float xy_scale_s = max0(js);
     const bool maxm = g.cfg.connection_method == 1;
@@ -391,7 +394,7 @@ __device__ __forceinline__ void connection_value(const GrowArgs &g, int img, int
         const float *cf = col_set(g, set, img, caf_i, dir);
         const int *off = col_offs(g, set, img, caf_i, dir);
         if (set) {
-            const RawSet raw = raw_set(g, img, caf_i, dir);
+            const RawSet raw = raw_set(g, img, caf_i, dir, ext);
             if (maxm)
                 grow_connection<true, true>(g, cf, raw, off, qx, qy, qs, r);
             else

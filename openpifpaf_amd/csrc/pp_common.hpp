@@ -335,7 +335,19 @@ struct HrMap {
         const float maxx = (float)ww - 1.0f, maxy = (float)hh - 1.0f;
         if (x < 0.0f || y < 0.0f || x > maxx || y > maxy) return dflt;
         if (x != x || y != y) return dflt;
-        const int ix = (int)x, iy = (int)y;
+        return value(plane, (int)x, (int)y);
+    }
+    // the same with the map's logical size (lh, lw) given: an image of a ragged batch
+    // (hr_dims) whose own map is smaller than the container the planes are stored in
+    __device__ __forceinline__ float at(int64_t plane, float x, float y, float dflt, int lh,
+                                        int lw) const {
+        const float maxx = (float)lw - 1.0f, maxy = (float)lh - 1.0f;
+        if (x < 0.0f || y < 0.0f || x > maxx || y > maxy) return dflt;
+        if (x != x || y != y) return dflt;
+        return value(plane, (int)x, (int)y);
+    }
+    // pixel (ix, iy) of the stored planes
+    __device__ __forceinline__ float value(int64_t plane, int ix, int iy) const {
         if (!masks) return base[(plane * hh + iy) * pitch + ix];
         const int64_t t = plane * tiles + (iy >> 6) * tiles_x + (ix >> 6);
         const int b = ((iy >> 3) & 7) * 8 + ((ix >> 3) & 7);
@@ -346,6 +358,23 @@ struct HrMap {
         return ((m >> b) & 1ull) ? v : 0.0f;
     }
 };
+
+// Ragged batches (pp_decode_ragged): the images of one batch share a container (H, W) and
+// every storage geometry derived from it (pitch, tiles, occupancy pitch, bucket grid), and
+// an (n_img, 2) device table `ext` holds each image's own field size (h_i, w_i).  The
+// image's own CifHr size decides three things only: the bounds of scalar_values
+// (HrMap::at), the clip of the splat boxes, and the occupancy grid's size.  ext NULL (every
+// uniform decode): the container's (hh, ww).  The decoder's kernels are bodies over `ext`
+// with two kernel wrappers each: the uniform one passes a literal NULL, so that its code is
+// what it was before the table existed; the *_ragged one passes the table.
+struct HrDims {
+    int hh, ww;
+};
+__device__ __forceinline__ HrDims hr_dims(const int32_t *ext, int64_t img, int stride, int hh,
+                                          int ww) {
+    if (!ext) return HrDims{hh, ww};
+    return HrDims{(ext[2 * img] - 1) * stride + 1, (ext[2 * img + 1] - 1) * stride + 1};
+}
 
 // dense map view of a caller's (n_img * K, hh, pitch) buffer
 inline HrMap dense_hr(const float *base, int hh, int ww) {
@@ -490,10 +519,11 @@ SeedSink seed_sink(int n_img, int K, const pp_config *cfg, int cap, void *scratc
 // splat of the field's list); launch_seeds then only sorts
 bool cifhr_fuses_seeds(const Heads &h, int n_img, int K, const pp_config *cfg);
 
-// `sink` (NULL: none): emit the seeds too (cifhr_fuses_seeds must hold)
+// `sink` (NULL: none): emit the seeds too (cifhr_fuses_seeds must hold); `ext` (NULL: none):
+// a ragged batch's extent table (hr_dims; one CIF head)
 int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config *cfg,
                         float *d_map, float *d_aux, uint64_t *d_masks, void *d_workspace,
                         size_t workspace_bytes, hipStream_t s, const char *who,
-                        const SeedSink *sink = nullptr);
+                        const SeedSink *sink = nullptr, const int32_t *ext = nullptr);
 
 }  // namespace pp

@@ -152,9 +152,9 @@ __device__ __noinline__ uint64_t spec_plan(SeedLoopShared &S, const pp_seed *see
 // NS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
 // directed edges: seed_loop_kernel<false, 1> needs 154 VGPRs and no spills where the two-slot
 // instance sits at the 168 cap with 28 (tools/resource_usage.py).
+// `ext` (hr_dims): NULL, or the images' own field sizes (seed_loop_ragged_kernel).
 template <bool CS, int NS>
-__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
-void seed_loop_kernel(GrowArgs g) {
+__device__ __forceinline__ void seed_loop_body(const GrowArgs &g, const int32_t *ext) {
     __shared__ SeedLDS Ls[kSeedWaves];
     __shared__ SeedLoopShared S;
     __shared__ int s_ncol[2 * PP_MAX_EDGES];  // set-A column counts per (CAF, direction)
@@ -194,8 +194,9 @@ void seed_loop_kernel(GrowArgs g) {
     pp_ann *cache = g.spec + (int64_t)img * kSpecCache;
     const float red = (float)g.cfg.occupancy_reduction;
     const float msr = occ_msr(g);
-    const OccGrid occ = occ_grid(occ_base, K, (int)((double)g.hh / g.cfg.occupancy_reduction),
-                                 (int)((double)g.ww / g.cfg.occupancy_reduction));
+    const HrDims dm = hr_dims(ext, img, g.heads.cstride[0], g.hh, g.ww);
+    const OccGrid occ = occ_grid(occ_base, K, (int)((double)dm.hh / g.cfg.occupancy_reduction),
+                                 (int)((double)dm.ww / g.cfg.occupancy_reduction));
     const int n_seeds = min(g.seed_counts[img], g.seed_cap);
     const pp_seed *seeds = g.seeds + (int64_t)img * g.seed_cap;
     // the occupancy at the seeds in LDS (seed_occ_*), or the global grid for more seeds
@@ -395,12 +396,34 @@ void seed_loop_kernel(GrowArgs g) {
     }
 }
 
+template <bool CS, int NS>
+__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
+void seed_loop_kernel(GrowArgs g) {
+    seed_loop_body<CS, NS>(g, nullptr);
+}
+
+template <bool CS, int NS>
+__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
+void seed_loop_ragged_kernel(GrowArgs g, const int32_t *ext) {
+    seed_loop_body<CS, NS>(g, ext);
+}
+
 // ---------------------------------------------------------------------------------------
 // host: the kernel's launcher (decode.hip has the rest of the host side)
 // ---------------------------------------------------------------------------------------
 // The seed loop of a decode whose images get no external helper workgroups (g.n_ext == 0).
-int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s) {
+int launch_seed_loop(const GrowArgs &g, int n_img, hipStream_t s, const int32_t *ext) {
     const size_t dyn = kColLds * sizeof(float);
+    if (ext) {  // a ragged batch: the same instances over the extent table
+        const dim3 rblk(64 * kSeedWaves);
+        if (g.has_cs)
+            hipLaunchKernelGGL((seed_loop_ragged_kernel<true, 2>), dim3(n_img), rblk, dyn, s, g, ext);
+        else if (g.nd <= 64)
+            hipLaunchKernelGGL((seed_loop_ragged_kernel<false, 1>), dim3(n_img), rblk, dyn, s, g, ext);
+        else
+            hipLaunchKernelGGL((seed_loop_ragged_kernel<false, 2>), dim3(n_img), rblk, dyn, s, g, ext);
+        return check_launch("pp_decode_ragged(seed loop)");
+    }
     // confidence_scales: their own kernel instances (the default ones carry no
     // registers for them: complete_kernel stays at 128 VGPRs, 4 waves per SIMD); they keep
     // the two-slot frontier at every skeleton size (fewer instances to compile)

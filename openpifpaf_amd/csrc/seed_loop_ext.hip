@@ -204,9 +204,9 @@ __device__ __forceinline__ void ext_refresh(SeedLoopSharedX &S, float *s_cols, c
 // 4% per planted cfg3 step when merged into it (spills inside the grow).
 // FS: frontier slots per lane (grow_frontier.hpp), 1 when the skeleton has at most 64
 // directed edges.
+// `ext` (hr_dims): NULL, or the images' own field sizes (seed_loop_ext_ragged_kernel).
 template <bool CS, int FS>
-__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
-void seed_loop_ext_kernel(GrowArgs g) {
+__device__ __forceinline__ void seed_loop_ext_body(const GrowArgs &g, const int32_t *ext) {
     constexpr int NS = kCacheSlots;
     __shared__ SeedLDS Ls[kSeedWaves];
     __shared__ SeedLoopSharedX S;
@@ -255,8 +255,9 @@ void seed_loop_ext_kernel(GrowArgs g) {
     pp_ann *cache = g.spec + (int64_t)img * kSpecCache;
     const float red = (float)g.cfg.occupancy_reduction;
     const float msr = occ_msr(g);
-    const OccGrid occ = occ_grid(occ_base, K, (int)((double)g.hh / g.cfg.occupancy_reduction),
-                                 (int)((double)g.ww / g.cfg.occupancy_reduction));
+    const HrDims dm = hr_dims(ext, img, g.heads.cstride[0], g.hh, g.ww);
+    const OccGrid occ = occ_grid(occ_base, K, (int)((double)dm.hh / g.cfg.occupancy_reduction),
+                                 (int)((double)dm.ww / g.cfg.occupancy_reduction));
     const int n_help = kSeedWaves + (X ? g.n_ext * kSeedWaves : 0);  // helper lanes 1 .. n_help-1
     // the occupancy at the seeds in LDS (seed_occ_*), or the global grid for more seeds
     const bool socc_on = !external && n_seeds <= kOccSeeds;  // block-uniform
@@ -593,14 +594,35 @@ void seed_loop_ext_kernel(GrowArgs g) {
     }
 }
 
+template <bool CS, int FS>
+__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
+void seed_loop_ext_kernel(GrowArgs g) {
+    seed_loop_ext_body<CS, FS>(g, nullptr);
+}
+
+template <bool CS, int FS>
+__global__ __launch_bounds__(64 * kSeedWaves) __attribute__((amdgpu_waves_per_eu(3)))
+void seed_loop_ext_ragged_kernel(GrowArgs g, const int32_t *ext) {
+    seed_loop_ext_body<CS, FS>(g, ext);
+}
+
 // ---------------------------------------------------------------------------------------
 // host: the kernel's launcher (decode.hip has the rest of the host side)
 // ---------------------------------------------------------------------------------------
 // The seed loop of a decode whose images get external helper workgroups (g.n_ext > 0).
-int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s) {
+int launch_seed_loop_ext(const GrowArgs &g, int n_img, hipStream_t s, const int32_t *ext) {
     // g.xext is zero: the workspace's zero region, which every external-helper seed
     // loop leaves zero (ext_exit)
     const dim3 grid(n_img * (1 + g.n_ext)), blk(64 * kSeedWaves);
+    if (ext) {  // a ragged batch: the same instances over the extent table
+        if (g.has_cs)
+            hipLaunchKernelGGL((seed_loop_ext_ragged_kernel<true, 2>), grid, blk, kExtDynLds, s, g, ext);
+        else if (g.nd <= 64)
+            hipLaunchKernelGGL((seed_loop_ext_ragged_kernel<false, 1>), grid, blk, kExtDynLds, s, g, ext);
+        else
+            hipLaunchKernelGGL((seed_loop_ext_ragged_kernel<false, 2>), grid, blk, kExtDynLds, s, g, ext);
+        return check_launch("pp_decode_ragged(seed loop)");
+    }
     if (g.has_cs)  // (two-slot at every skeleton size, as in launch_seed_loop)
         hipLaunchKernelGGL((seed_loop_ext_kernel<true, 2>), grid, blk, kExtDynLds, s, g);
     else if (g.nd <= 64)

@@ -936,7 +936,8 @@ constexpr int kHrSt = 12;
 // candidates (c, x, y, s; c > threshold, in cell order) are in the sink's segment: v =
 // 0.9 * CifHr(x, y) + 0.1 * c from the finished block-sparse map, the seeds with v above
 // the threshold compacted in place, in order; their count into f_counts.  Block-uniform.
-__device__ void seeds_from_map(const HrSparseArgs &a, int64_t fld, int n_seed, int *s_tmp) {
+__device__ void seeds_from_map(const HrSparseArgs &a, const HrDims dm, int64_t fld, int n_seed,
+                               int *s_tmp) {
     const SeedSink &ss = a.seeds;
     const int hw = a.h.cH[0] * a.h.cW[0];
     const int f = (int)(fld % ss.K);
@@ -946,8 +947,8 @@ __device__ void seeds_from_map(const HrSparseArgs &a, int64_t fld, int n_seed, i
     HrMap hm{};
     hm.base = a.map;
     hm.masks = a.masks;
-    hm.hh = a.hh;
-    hm.ww = a.ww;
+    hm.hh = dm.hh;
+    hm.ww = dm.ww;
     hm.tiles_x = a.tiles_x;
     hm.tiles = a.tiles;
     int kept = 0;
@@ -1010,7 +1011,8 @@ __device__ void seeds_from_map(const HrSparseArgs &a, int64_t fld, int n_seed, i
 // cif_seeds.py:28-33) into a.seeds' segment in cell order, their count into f_counts[fld]
 // (seeds_from_map finishes them); s_tmp: 4 ints of LDS.
 template <bool MULTI, bool SEEDS = false, int STAGE = kSpStage>
-__device__ int hr_splat_list(const HrSparseArgs &a, int64_t fld, int64_t slot, uint32_t *s_bits,
+__device__ int hr_splat_list(const HrSparseArgs &a, const HrDims dm, int64_t fld, int64_t slot,
+                             uint32_t *s_bits,
                              int (*s_cnt)[kSpU][4], int *s_gbeg, int *stage,
                              int *s_tmp = nullptr) {
     static_assert(!(MULTI && SEEDS), "seed candidates of one CIF head only");
@@ -1053,8 +1055,8 @@ __device__ int hr_splat_list(const HrSparseArgs &a, int64_t fld, int64_t slot, u
             const float sg = (0.5f * s4) * stride;
             const float sigma = (sg != sg) ? sg : fmaxf(1.0f, sg);  // np.maximum keeps NaN
             const float v = (c / a.neighbors) / len_cifs;           // v / neighbors / len_cifs
-            const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, a.hh, a.ww);
-            glist[pos] = make_cand(box, make_float4(cx, cy, v, sigma * sigma), a.hh, a.ww);
+            const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, dm.hh, dm.ww);
+            glist[pos] = make_cand(box, make_float4(cx, cy, v, sigma * sigma), dm.hh, dm.ww);
             for (int ty = box.z / kTile; ty <= (box.w - 1) / kTile; ty++)
                 for (int tx = box.x / kTile; tx <= (box.y - 1) / kTile; tx++) {
                     const int t = ty * a.tiles_x + tx;
@@ -1169,8 +1171,10 @@ __device__ int hr_splat_list(const HrSparseArgs &a, int64_t fld, int64_t slot, u
 // uniform dense map 5.36 -> 5.32 ms per 256 images against 98 VGPRs, planted unchanged.
 // SEEDS: the seed candidates too (hr_splat_list), and the field's completion counter of
 // cifhr_sparse_kernel<false, true> zeroed (the kernel boundary orders it before that launch).
+// `ext`, K (hr_dims): NULL, or the images' own field sizes (cifhr_list_ragged_kernel) and
+// the fields per image.
 template <bool SEEDS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_list_kernel(HrSparseArgs a) {
+__device__ __forceinline__ void cifhr_list_body(const HrSparseArgs &a, const int32_t *ext, int K) {
     __shared__ uint32_t s_bits[kTileBits / 32];
     __shared__ RowBinLds s_rb;
     __shared__ __attribute__((aligned(16))) int s_cnt[2][kSpU][4];
@@ -1181,10 +1185,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
     __shared__ int s_stage[kStage];
     __shared__ int s_tmp[4];
     const int64_t fld = blockIdx.x;
+    const HrDims dm = hr_dims(ext, ext ? fld / K : 0, a.h.cstride[0], a.hh, a.ww);
     if (threadIdx.x < kTileBits / 32) s_bits[threadIdx.x] = 0u;
     if (SEEDS && threadIdx.x == 0) a.done[fld] = 0;
     const int total =
-        hr_splat_list<false, SEEDS, kStage>(a, fld, fld, s_bits, s_cnt, s_gbeg, s_stage, s_tmp);
+        hr_splat_list<false, SEEDS, kStage>(a, dm, fld, fld, s_bits, s_cnt, s_gbeg, s_stage, s_tmp);
     int *rowcnt = a.pre_rowcnt + fld * kMaxBinRows, *rowoff = a.pre_rowoff + fld * kMaxBinRows;
     if (a.bins_cap > 0 && total > kBinMin)
         hr_row_bins(a.list + fld * a.list_cap, total, a.bins + fld * a.bins_cap, a.bins_cap,
@@ -1198,6 +1203,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
             if (!((s_bits[t >> 5] >> (t & 31)) & 1u)) a.masks[fld * a.tiles + t] = 0ull;
 }
 
+template <bool SEEDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_list_kernel(HrSparseArgs a) {
+    cifhr_list_body<SEEDS>(a, nullptr, 0);
+}
+
+template <bool SEEDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void cifhr_list_ragged_kernel(HrSparseArgs a, const int32_t *ext, int K) {
+    cifhr_list_body<SEEDS>(a, ext, K);
+}
+
 // SEEDS (split fields with a prebuilt list and seed candidates, cifhr_list_kernel<true>):
 // the field's last workgroup to finish its fold emits the field's seeds (seeds_from_map).
 // Completion is the write-through counter form of cdna_hip_programming.md Guideline 16: the
@@ -1208,7 +1224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
 // every workgroup instead, cfg2 uniform's fold kernel took 99-110 vs 70 us.)
 template <bool MULTI, bool SEEDS = false>
 // 8 waves per SIMD (<= 64 VGPRs): the kernel is latency-bound, occupancy hides it
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_sparse_kernel(HrSparseArgs a) {
+__device__ __forceinline__ void cifhr_sparse_body(const HrSparseArgs &a, const int32_t *ext, int K) {
     static_assert(!(MULTI && SEEDS), "seeds of one CIF head only");
     __shared__ uint32_t s_bits[kTileBits / 32];
     __shared__ RowBinLds s_rb;
@@ -1223,6 +1239,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
 
     const int64_t fld = blockIdx.x / a.split;  // image * K + field
     const int part = (int)(blockIdx.x % a.split);
+    const HrDims dm = hr_dims(ext, ext ? fld / K : 0, a.h.cstride[0], a.hh, a.ww);
     const bool pre = !MULTI && a.pre_total;
     // list / bins copy of this workgroup (fld * split + part), or the field's prebuilt one
     const int64_t slot = pre ? fld : (int64_t)blockIdx.x;
@@ -1245,7 +1262,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
         __syncthreads();
     } else {
         if (threadIdx.x < kTileBits / 32) s_bits[threadIdx.x] = 0u;
-        total = hr_splat_list<MULTI>(a, fld, slot, s_bits, s_cnt, s_gbeg,
+        total = hr_splat_list<MULTI>(a, dm, fld, slot, s_bits, s_cnt, s_gbeg,
                                      reinterpret_cast<int *>(&s_cand[0][0]));
         use_bins = !MULTI && a.bins_cap > 0 && total > kBinMin;
         if (use_bins)
@@ -1367,7 +1384,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
             for (uint64_t rest = live; rest; rest &= rest - 1) {
                 const int blk = __builtin_ctzll(rest);
                 const int px = tx0 + 8 * (blk & 7) + lx, py = ty0 + 8 * (blk >> 3) + ly;
-                const bool on = px < a.ww && py < a.hh;
+                const bool on = px < dm.ww && py < dm.hh;
                 const float fx = on ? (float)px : kOffMapCoord, fy = on ? (float)py : kOffMapCoord;
                 const uint32_t key = on ? pix_key(px, py) : kOffMapKey;
                 const uint64_t bq = __ballot((cl >> blk) & 1ull);
@@ -1468,9 +1485,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
         __syncthreads();
         if (s_last) {
             int *s_tmp = reinterpret_cast<int *>(&s_cand[0][0]);  // the fold's LDS is free
-            seeds_from_map(a, fld, a.seeds.f_counts[fld], s_tmp);
+            seeds_from_map(a, dm, fld, a.seeds.f_counts[fld], s_tmp);
         }
     }
+}
+
+template <bool MULTI, bool SEEDS = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_sparse_kernel(HrSparseArgs a) {
+    cifhr_sparse_body<MULTI, SEEDS>(a, nullptr, 0);
+}
+
+// one CIF head (the ragged decode is single-scale)
+template <bool SEEDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void cifhr_sparse_ragged_kernel(HrSparseArgs a, const int32_t *ext, int K) {
+    cifhr_sparse_body<false, SEEDS>(a, ext, K);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1500,7 +1529,8 @@ constexpr int kFuList = 256;   // fold candidates of a field held in LDS
 constexpr int kFuStage = 512;  // kept cells of a round staged in LDS
 
 template <bool LDS>
-__device__ __forceinline__ void fused_phase2(const HrSparseArgs &a, int64_t fld, int total,
+__device__ __forceinline__ void fused_phase2(const HrSparseArgs &a, const HrDims dm, int64_t fld,
+                                             int total,
                                              bool use_bins, const FoldCand *s_list,
                                              FoldCand *cand, uint8_t *idx,
                                              const uint32_t *s_bits, const int *s_rowcnt,
@@ -1585,7 +1615,7 @@ __device__ __forceinline__ void fused_phase2(const HrSparseArgs &a, int64_t fld,
             for (uint64_t rest = live; rest; rest &= rest - 1) {
                 const int blk = __builtin_ctzll(rest);
                 const int px = tx0 + 8 * (blk & 7) + lx, py = ty0 + 8 * (blk >> 3) + ly;
-                const bool on = px < a.ww && py < a.hh;
+                const bool on = px < dm.ww && py < dm.hh;
                 const float fx = on ? (float)px : kOffMapCoord, fy = on ? (float)py : kOffMapCoord;
                 const uint32_t key = on ? pix_key(px, py) : kOffMapKey;
                 const uint64_t bq = __ballot((cl >> blk) & 1ull);
@@ -1602,7 +1632,7 @@ __device__ __forceinline__ void fused_phase2(const HrSparseArgs &a, int64_t fld,
 }
 
 template <bool SEEDS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_fused_kernel(HrSparseArgs a) {
+__device__ __forceinline__ void cifhr_fused_body(const HrSparseArgs &a, const int32_t *ext, int K) {
     // the field's list (<= kFuList entries), or with a longer list the per-wave candidate
     // copies of phase 2
     __shared__ __attribute__((aligned(16))) FoldCand s_list[kFuList];
@@ -1618,6 +1648,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
     __shared__ int s_next;
 
     const int64_t fld = blockIdx.x;  // image * K + field
+    const HrDims dm = hr_dims(ext, ext ? fld / K : 0, a.h.cstride[0], a.hh, a.ww);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave == 0) HR_STAMP(0);
     if (threadIdx.x == 0) s_next = 0;
@@ -1646,8 +1677,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
         const float sg = (0.5f * s4) * stride;
         const float sigma = (sg != sg) ? sg : fmaxf(1.0f, sg);  // np.maximum keeps NaN
         const float v = (c / a.neighbors) / 1.0f;                 // v / neighbors / len_cifs
-        const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, a.hh, a.ww);
-        const FoldCand fc = make_cand(box, make_float4(cx, cy, v, sigma * sigma), a.hh, a.ww);
+        const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, dm.hh, dm.ww);
+        const FoldCand fc = make_cand(box, make_float4(cx, cy, v, sigma * sigma), dm.hh, dm.ww);
         if (pos < kFuList)
             s_list[pos] = fc;
         else
@@ -1769,17 +1800,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
 
     // ---- phase 2: the waves take the touched tiles from an LDS counter ----
     if (lds)
-        fused_phase2<true>(a, fld, total, false, s_list, nullptr, s_idx[wave], s_bits, s_rowcnt,
+        fused_phase2<true>(a, dm, fld, total, false, s_list, nullptr, s_idx[wave], s_bits, s_rowcnt,
                            s_rowoff, s_live, &s_next);
     else
-        fused_phase2<false>(a, fld, total, use_bins, nullptr, s_list + wave * kSpCand, nullptr,
+        fused_phase2<false>(a, dm, fld, total, use_bins, nullptr, s_list + wave * kSpCand, nullptr,
                             s_bits, s_rowcnt, s_rowoff, s_live, &s_next);
 
     // ---- phase 3: the seeds (cif_seeds.py:35-47) from the finished map ----
     if constexpr (SEEDS) {
         __syncthreads();  // every wave's blocks and masks are stored
         if (wave == 0) HR_STAMP(2);
-        if (seeding) seeds_from_map(a, fld, n_seed, s_tmp);
+        if (seeding) seeds_from_map(a, dm, fld, n_seed, s_tmp);
         else if (threadIdx.x == 0) ss.f_counts[fld] = 0;
     }
 #ifdef PP_STAMPS
@@ -1790,6 +1821,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
         g_hr_stamps[blockIdx.x * kHrSt + 7] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
     }
 #endif
+}
+
+template <bool SEEDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cifhr_fused_kernel(HrSparseArgs a) {
+    cifhr_fused_body<SEEDS>(a, nullptr, 0);
+}
+
+template <bool SEEDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void cifhr_fused_ragged_kernel(HrSparseArgs a, const int32_t *ext, int K) {
+    cifhr_fused_body<SEEDS>(a, ext, K);
 }
 
 // -------------------------------------------------------------------------------------
@@ -2013,7 +2055,7 @@ bool cifhr_fuses_seeds(const Heads &h, int n_img, int K, const pp_config *cfg) {
 int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config *cfg,
                         float *d_map, float *d_aux, uint64_t *d_masks, void *d_workspace,
                         size_t workspace_bytes, hipStream_t s, const char *who,
-                        const SeedSink *sink) {
+                        const SeedSink *sink, const int32_t *ext) {
     if (!cfg || !d_map || !d_masks || !d_workspace || (h.n_groups > 1 && !d_aux))
         return fail(PP_EINVAL, std::string(who) + ": NULL argument");
     for (int m = 0; m < h.n_cif; m++)
@@ -2028,6 +2070,8 @@ int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_confi
     const HrMap geo = dense_hr(nullptr, hh, ww);
     if (geo.tiles > kTileBits) return fail(PP_ESHAPE, std::string(who) + ": CifHr map too large");
     if (h.n_groups > 8) return fail(PP_ESHAPE, std::string(who) + ": too many CifHr groups");
+    if (ext && (h.n_cif != 1 || h.n_groups != 1 || h.group_size() != 1))
+        return fail(PP_EINVAL, std::string(who) + ": a ragged batch has one CIF head");
     HrSparseArgs a{};
     a.h = h;
     a.hh = hh;
@@ -2080,7 +2124,12 @@ int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_confi
             if (!cifhr_fuses_seeds(h, n_img, K, cfg) || sink->K != K)
                 return fail(PP_EINVAL, std::string(who) + ": seeds cannot be fused here");
             a.seeds = *sink;
-            hipLaunchKernelGGL(cifhr_fused_kernel<true>, dim3(nblocks), dim3(256), 0, s, a);
+            if (ext)
+                hipLaunchKernelGGL(cifhr_fused_ragged_kernel<true>, dim3(nblocks), dim3(256), 0, s, a, ext, K);
+            else
+                hipLaunchKernelGGL(cifhr_fused_kernel<true>, dim3(nblocks), dim3(256), 0, s, a);
+        } else if (ext) {
+            hipLaunchKernelGGL(cifhr_fused_ragged_kernel<false>, dim3(nblocks), dim3(256), 0, s, a, ext, K);
         } else {
             hipLaunchKernelGGL(cifhr_fused_kernel<false>, dim3(nblocks), dim3(256), 0, s, a);
         }
@@ -2106,12 +2155,21 @@ int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_confi
         a.done = a.pre_rowoff + nf * kMaxBinRows;
         if (sink) {
             a.seeds = *sink;
-            hipLaunchKernelGGL(cifhr_list_kernel<true>, dim3((unsigned)nf), dim3(256), 0, s, a);
+            if (ext)
+                hipLaunchKernelGGL(cifhr_list_ragged_kernel<true>, dim3((unsigned)nf), dim3(256), 0, s, a, ext, K);
+            else
+                hipLaunchKernelGGL(cifhr_list_kernel<true>, dim3((unsigned)nf), dim3(256), 0, s, a);
+        } else if (ext) {
+            hipLaunchKernelGGL(cifhr_list_ragged_kernel<false>, dim3((unsigned)nf), dim3(256), 0, s, a, ext, K);
         } else {
             hipLaunchKernelGGL(cifhr_list_kernel<false>, dim3((unsigned)nf), dim3(256), 0, s, a);
         }
     }
-    if (h.n_groups > 1)
+    if (ext && sink)
+        hipLaunchKernelGGL(cifhr_sparse_ragged_kernel<true>, dim3(nblocks), dim3(256), 0, s, a, ext, K);
+    else if (ext)
+        hipLaunchKernelGGL(cifhr_sparse_ragged_kernel<false>, dim3(nblocks), dim3(256), 0, s, a, ext, K);
+    else if (h.n_groups > 1)
         hipLaunchKernelGGL(cifhr_sparse_kernel<true>, dim3(nblocks), dim3(256), 0, s, a);
     else if (sink)
         hipLaunchKernelGGL((cifhr_sparse_kernel<false, true>), dim3(nblocks), dim3(256), 0, s, a);

@@ -122,7 +122,8 @@ struct SeedArgs {
 constexpr int kEmitU = 32;
 constexpr int kEmitStage = 256 * kEmitU;  // a whole round: no fallback for one 80x80 field
 
-__global__ __launch_bounds__(256) void seeds_emit_kernel(SeedArgs a) {
+// `ext` (hr_dims): NULL, or the images' own field sizes (seeds_emit_ragged_kernel).
+__device__ __forceinline__ void seeds_emit_body(const SeedArgs &a, const int32_t *ext) {
     __shared__ int s_tmp[4];
     __shared__ __attribute__((aligned(16))) int s_cnt[kEmitU][4];
     __shared__ int s_stage[kEmitStage];
@@ -153,7 +154,8 @@ __global__ __launch_bounds__(256) void seeds_emit_kernel(SeedArgs a) {
         if (ms_on && !(sc > ms_th)) return false;  // then p[4] > min_scale / stride
         x = x * stride;
         y = y * stride;
-        const float hv = a.hr.at(plane, x, y, 0.0f);
+        const HrDims dm = hr_dims(ext, img, a.h.cstride[0], a.hr.hh, a.hr.ww);
+        const float hv = a.hr.at(plane, x, y, 0.0f, dm.hh, dm.ww);
         float vv = 0.9f * hv + 0.1f * c;  // 0.9 * v + 0.1 * c
         if (a.score_scale != 1.0f) vv = vv * a.score_scale;
         v = vv;
@@ -237,6 +239,12 @@ __global__ __launch_bounds__(256) void seeds_emit_kernel(SeedArgs a) {
         __syncthreads();  // s_cnt / s_stage are rewritten by the next round
     }
     if (threadIdx.x == 0) a.f_counts[blockIdx.x] = running;
+}
+
+__global__ __launch_bounds__(256) void seeds_emit_kernel(SeedArgs a) { seeds_emit_body(a, nullptr); }
+
+__global__ __launch_bounds__(256) void seeds_emit_ragged_kernel(SeedArgs a, const int32_t *ext) {
+    seeds_emit_body(a, ext);
 }
 
 // Seeds with v > threshold > 0 sort as 64-bit keys, descending: v's bits (positive
@@ -1073,8 +1081,10 @@ struct StashCol {
     int bucket;
 };
 
+// `ext` (hr_dims): NULL, or the images' own field sizes (caf_bucketed_ragged_kernel; set A
+// only: the index-only sets look nothing up in the map).
 template <bool INDEX_ONLY, bool STASH>
-__global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_kernel(CafBArgs a) {
+__device__ __forceinline__ void caf_bucketed_body(const CafBArgs &a, const int32_t *ext) {
     constexpr int NT = STASH && INDEX_ONLY ? 512 : 256;
     constexpr int NW = NT / 64;
     // The set-B build (PK) keeps its LDS small enough to run beside a seed-loop workgroup
@@ -1125,6 +1135,7 @@ __global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_
     const bool use2 = need_f && a.cif_floor < 1.0f && j2i < a.K;
     const int64_t t1 = (int64_t)img * a.K + (use1 ? j1i : 0);
     const int64_t t2 = (int64_t)img * a.K + (use2 ? j2i : 0);
+    const HrDims dm = hr_dims(ext, img, a.h.cstride[0], a.hr.hh, a.hr.ww);
     for (int i = threadIdx.x; i < (PK ? (nb + 2) / 2 : nb + 1); i += NT) {
         s_cnt[0][i] = 0;
         s_cnt[1][i] = 0;
@@ -1184,9 +1195,9 @@ __global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_
             const float score = B.nine[k][0];
             float sb = score, sf = score;
             if (use1)
-                sb = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t1, B.nine[k][1], B.nine[k][2], 0.0f));
+                sb = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t1, B.nine[k][1], B.nine[k][2], 0.0f, dm.hh, dm.ww));
             if (use2)
-                sf = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t2, B.nine[k][5], B.nine[k][6], 0.0f));
+                sf = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t2, B.nine[k][5], B.nine[k][6], 0.0f, dm.hh, dm.ww));
             B.sb[k] = sb;
             B.sf[k] = sf;
             B.kb[k] = need_b && sb > a.th;
@@ -1318,9 +1329,9 @@ __global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_
                 const float score = B.nine[k][0];
                 float sb = score, sf = score;
                 if (use1)
-                    sb = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t1, B.nine[k][1], B.nine[k][2], 0.0f));
+                    sb = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t1, B.nine[k][1], B.nine[k][2], 0.0f, dm.hh, dm.ww));
                 if (use2)
-                    sf = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t2, B.nine[k][5], B.nine[k][6], 0.0f));
+                    sf = score * (a.cif_floor + a.one_minus_floor * a.hr.at(t2, B.nine[k][5], B.nine[k][6], 0.0f, dm.hh, dm.ww));
                 B.sb[k] = sb;
                 B.sf[k] = sf;
                 B.kb[k] = need_b && sb > a.th;
@@ -1473,6 +1484,15 @@ __global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_
     }
 }
 
+template <bool INDEX_ONLY, bool STASH>
+__global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_kernel(CafBArgs a) {
+    caf_bucketed_body<INDEX_ONLY, STASH>(a, nullptr);
+}
+
+__global__ __launch_bounds__(256) void caf_bucketed_ragged_kernel(CafBArgs a, const int32_t *ext) {
+    caf_bucketed_body<false, true>(a, ext);
+}
+
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 SeedSink seed_sink(int n_img, int K, const pp_config *cfg, int cap, void *scratch) {
@@ -1495,7 +1515,7 @@ SeedSink seed_sink(int n_img, int K, const pp_config *cfg, int cap, void *scratc
 // SeedSink): only the sort runs
 int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_config *cfg,
                  pp_seed *seeds, int cap, int *counts, void *scratch, hipStream_t s,
-                 bool emitted) {
+                 bool emitted, const int32_t *ext = nullptr) {
     if (K > PP_MAX_KP) return fail(PP_ESHAPE, "seeds: more than PP_MAX_KP CIF fields");
     if ((int64_t)cap < (int64_t)K * h.cif_cells())
         return fail(PP_ESHAPE, "seeds: capacity < K * cells");
@@ -1520,7 +1540,9 @@ int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_con
     a.f_counts = (int *)w;
     w += round_up((int64_t)n_img * kMaxHeads * PP_MAX_KP * sizeof(int), 256);
     a.g_perm = (int *)w;
-    if (!emitted)
+    if (!emitted && ext)
+        hipLaunchKernelGGL(seeds_emit_ragged_kernel, dim3((unsigned)((int64_t)n_img * h.n_cif * K)), dim3(256), 0, s, a, ext);
+    else if (!emitted)
         hipLaunchKernelGGL(seeds_emit_kernel, dim3((unsigned)((int64_t)n_img * h.n_cif * K)), dim3(256), 0, s, a);
 #ifdef PP_STAMPS
     uint64_t *st = nullptr;
@@ -1600,7 +1622,8 @@ void caf_bucket_grid(int H, int W, int stride, int *bw, int *bh, int *nb, float 
 
 int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C,
                         const int32_t *skeleton, const pp_config *cfg, float th, float *cols,
-                        int *offs, const int *gate, bool index_only, hipStream_t s) {
+                        int *offs, const int *gate, bool index_only, hipStream_t s,
+                        const int32_t *ext) {
     if (C > kMaxCaf) return fail(PP_ESHAPE, "caf_scored: more than PP_MAX_EDGES CAF fields");
     CafBArgs a{};
     a.h = h;
@@ -1625,6 +1648,8 @@ int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C
                            (size_t)(2 * a.col_cap * sizeof(uint16_t)), s, a);
     else if (index_only)
         hipLaunchKernelGGL((caf_bucketed_kernel<true, false>), grid, dim3(256), 0, s, a);
+    else if (ext)
+        hipLaunchKernelGGL(caf_bucketed_ragged_kernel, grid, dim3(256), 0, s, a, ext);
     else
         hipLaunchKernelGGL((caf_bucketed_kernel<false, true>), grid, dim3(256), 0, s, a);
     return check_launch("caf_scored(bucketed)");

@@ -17,7 +17,7 @@ from ... import _device
 from ..._abi import PACK_ALL, check_seed_mask, make_config, skeleton_array
 from ...annotation import Annotation
 from ...distributed import decode_sharded, shard
-from ...engine import HeadSet, InitialAnnotations, engine
+from ...engine import HeadSet, InitialAnnotations, RaggedFields, engine
 from ...functional import grow_connection_blend
 from .. import nms as nms_module
 from ..caf_scored import CafScored
@@ -271,16 +271,51 @@ class CifCaf(Generator):
                             for i, h in enumerate(heads)], self.field_config)
         return self._coco(None, None, head_set, metas, params)
 
-    def _coco(self, cif, caf, heads, metas, params):
+    # -- ragged batches: images of different field sizes -----------------------------------
+    def _ragged(self, fields_list, kw):
+        """RaggedFields of a list of per-image head lists (Generator.fields_batch entries, each
+        read through the single-scale FieldConfig), packed on the device."""
+        for name in ('group', 'initial_annotations', 'keep_cifhr'):
+            if kw.pop(name, None):
+                raise NotImplementedError(
+                    'a ragged batch does not take {}: its decode is single-GPU, starts from '
+                    'the seeds and keeps no dense CifHr map'.format(name))
+        if kw:
+            raise TypeError('unexpected arguments: ' + ', '.join(sorted(kw)))
+        if not self.field_config.is_single_scale():
+            raise NotImplementedError('a ragged batch needs a single-scale FieldConfig (one '
+                                      'CIF and one CAF head); multi-scale heads are not built')
+        cif_i, caf_i, _ = self.field_config.single_scale()
+        return RaggedFields([(_device.to_device(f[cif_i]), _device.to_device(f[caf_i]))
+                             for f in fields_list])
+
+    def decode_ragged(self, fields_list, **kw):
+        """One entry per image, each image's head outputs [cif (K, 5, h_i, w_i), caf (C, 9,
+        h_i, w_i), ...] at its OWN size (what Generator.fields_batch returns, from any
+        number of forward passes) -> one list of Annotation per image, each as __call__
+        gives it for that image alone, decoded as one device batch (pp_decode_ragged)."""
+        ragged = self._ragged(fields_list, kw)
+        recs, offsets, _ = engine().decode(None, None, skeleton_array(self.skeleton),
+                                           self.config(), compact=PACK_ALL, ragged=ragged)
+        return self.annotations_from_records(recs, offsets)
+
+    def coco_ragged(self, fields_list, metas, **params):
+        """coco_batch for images of different field sizes (decode_ragged's `fields_list`)."""
+        ragged = self._ragged(fields_list, {k: params.pop(k) for k in
+                                            ('group', 'initial_annotations', 'keep_cifhr')
+                                            if k in params})
+        return self._coco(None, None, None, metas, params, ragged=ragged)
+
+    def _coco(self, cif, caf, heads, metas, params, ragged=None):
         from ...eval_coco import metas_device  # pylint: disable=import-outside-toplevel
         if self.nms is not None and not self._device_nms():
             raise TypeError('coco_batch needs the device NMS (nms.Keypoints or None): a host '
                             'NMS object leaves no device records')
-        n = len(cif) if heads is None else heads.n
+        n = ragged.n if ragged is not None else len(cif) if heads is None else heads.n
         if len(metas) != n:
             raise ValueError('{} metas for {} images'.format(len(metas), n))
         b = engine().launch_checked(cif, caf, skeleton_array(self.skeleton), self.config(),
-                                    heads=heads)
+                                    heads=heads, ragged=ragged)
         d_metas, d_ids, d_swap = metas_device(metas, len(self.keypoints))
         return engine().fetch_coco_async(b, d_metas, d_ids, hswap=d_swap, **params).result()
 

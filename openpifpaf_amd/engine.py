@@ -156,6 +156,62 @@ class HeadSet:
             (s.H, s.W, s.stride, s.role) for s in self.arr)
 
 
+class RaggedFields:
+    """A batch of images of different field sizes (pp_fields_pack_ragged): `fields` is a list
+    of per-image (cif, caf) device tensors, float32 and contiguous, (K, 5, h_i, w_i) and
+    (C, 9, h_i, w_i) with K and C the same for every image.  Packs them on the current stream
+    into the containers `cif` (n, K, 5, H, W) and `caf` (n, C, 9, H, W), (H, W) the largest
+    size, zero outside each image's extent, and owns them with the extent table (`extents`,
+    device (n, 2) int32; `extents_host` the same on the host).  The images' tensors may be
+    freed once the pack has run.  A list of equal shapes takes the same route."""
+
+    def __init__(self, fields):
+        lib = load()
+        fields = [tuple(f) for f in fields]
+        if not fields:
+            raise ValueError('a ragged batch needs at least one image')
+        for f in fields:
+            if len(f) != 2 or not all(_device.is_device(t) and t.dtype == torch.float32 and
+                                      t.is_contiguous() and t.dim() == 4 for t in f):
+                raise ValueError('ragged fields must be (cif, caf) pairs of contiguous float32 '
+                                 'device tensors (K, 5, h, w) and (C, 9, h, w)')
+            if f[0].shape[1] != 5 or f[1].shape[1] != 9 or f[0].shape[2:] != f[1].shape[2:]:
+                raise ValueError('expected cif (K, 5, h, w) and caf (C, 9, h, w) of one spatial '
+                                 'shape per image, got {} and {}'.format(tuple(f[0].shape),
+                                                                         tuple(f[1].shape)))
+        self.n = n = len(fields)
+        self.k, self.c = fields[0][0].shape[0], fields[0][1].shape[0]
+        if any(f[0].shape[0] != self.k or f[1].shape[0] != self.c for f in fields):
+            raise ValueError('the images of a ragged batch differ in K or C: ' + ', '.join(
+                sorted({'K={} C={}'.format(f[0].shape[0], f[1].shape[0]) for f in fields})))
+        self.extents_host = np.array([f[0].shape[2:] for f in fields], np.int32).reshape(n, 2)
+        self.h, self.w = (int(v) for v in self.extents_host.max(axis=0))
+        dev = fields[0][0].device
+        self.cif = torch.empty((n, self.k, 5, self.h, self.w), dtype=torch.float32, device=dev)
+        self.caf = torch.empty((n, self.c, 9, self.h, self.w), dtype=torch.float32, device=dev)
+        # pinned host tables (pointers, then extents, per field kind): the copies are
+        # asynchronous, so the tables live as long as this object
+        size, ext_off = lib.pp_ragged_tables_size(n), lib.pp_ragged_extents_offset(n)
+        self._host = torch.empty((2, size), dtype=torch.uint8, pin_memory=True)
+        self._tables = torch.empty((2, size), dtype=torch.uint8, device=dev)
+        for kind in range(2):
+            host = self._host[kind].numpy()
+            host[:ext_off].view(np.uint64)[:] = [f[kind].data_ptr() for f in fields]
+            host[ext_off:].view(np.int32)[:] = self.extents_host.reshape(-1)
+        self.extents = self._tables[0][ext_off:].view(torch.int32).view(n, 2)
+        self.pack()
+
+    def pack(self):
+        """The two pack launches (CIF, then CAF) on the current stream, from the tables built
+        at construction: again after the images' tensors were rewritten in place."""
+        size, ext_off = self._host.shape[1], load().pp_ragged_extents_offset(self.n)
+        for kind, (out, planes, ch) in enumerate(((self.cif, self.k, 5), (self.caf, self.c, 9))):
+            call('pp_fields_pack_ragged', ctypes.c_void_p(self._host[kind].data_ptr()),
+                 ctypes.c_void_p(self._host[kind].data_ptr() + ext_off), self.n, planes, ch,
+                 self.h, self.w, _device.ptr(out), _device.ptr(self._tables[kind]),
+                 ctypes.c_size_t(size), _device.stream())
+
+
 def _buffer_key(n, k, c, shape, cap, cfg):
     return (n, k, c, shape, cap, cfg.force_complete, cfg.stride, cfg.occupancy_reduction)
 
@@ -225,6 +281,26 @@ class DecodeEngine:
              _device.ptr(b.out_index), _device.ptr(b.ws), ctypes.c_size_t(b.ws.numel()),
              ctypes.c_uint32(stages), _device.stream())
 
+    def launch_ragged(self, ragged, skeleton, cfg, cap=None, stages=STAGE_ALL):
+        """pp_decode_ragged over a RaggedFields, with launch's buffers at the container's
+        shape; returns the DecodeBuffers."""
+        skel = skeleton_array(skeleton)
+        if len(skel) != ragged.c:
+            raise ValueError('skeleton has {} edges but caf has {} fields'.format(len(skel),
+                                                                                  ragged.c))
+        n, k, c, h, w = ragged.n, ragged.k, ragged.c, ragged.h, ragged.w
+        cap = cap or default_ann_capacity(h, w)
+        b = self.buffers(n, k, c, h, w, cfg, cap)
+        if stages & STAGE_GROW and not stages & STAGE_AFTER_SEED_LOOP:
+            b.next_slot()
+        call('pp_decode_ragged', _device.ptr(ragged.cif), _device.ptr(ragged.caf), n, k, c, h, w,
+             _device.ptr(ragged.extents), ragged.extents_host.ctypes.data_as(ctypes.c_void_p),
+             skel.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cfg), ctypes.c_void_p(0),
+             _device.ptr(b.anns), cap, _device.ptr(b.counts), _device.ptr(b.status),
+             _device.ptr(b.ws), ctypes.c_size_t(b.ws.numel()), ctypes.c_uint32(stages),
+             _device.stream())
+        return b
+
     def launch_multi(self, heads, skeleton, cfg, cap=None, keep_cifhr=False, stages=STAGE_ALL,
                      initial=None):
         """pp_decode_multi over a HeadSet (pp_decode_initial with `initial`); returns the
@@ -250,15 +326,28 @@ class DecodeEngine:
         return b
 
     def launch_checked(self, cif, caf, skeleton, cfg, cap=None, keep_cifhr=False, heads=None,
-                       initial=None):
-        """launch / launch_multi with overflow retry (the annotation capacity doubles until
-        no image overflows); returns the DecodeBuffers of a decode whose records are
-        complete.  Raises PPError on the overflows a retry cannot fix."""
-        h, w = (cif.shape[3], cif.shape[4]) if heads is None else (heads.h, heads.w)
+                       initial=None, ragged=None):
+        """launch / launch_multi / launch_ragged with overflow retry (the annotation capacity
+        doubles until no image overflows); returns the DecodeBuffers of a decode whose
+        records are complete.  Raises PPError on the overflows a retry cannot fix.  With a
+        RaggedFields `ragged`, cif / caf are ignored."""
+        if ragged is not None:
+            if heads is not None:
+                raise NotImplementedError('a ragged batch is single-scale (no HeadSet)')
+            if initial is not None:
+                raise NotImplementedError('a ragged batch takes no initial annotations')
+            if keep_cifhr:
+                raise NotImplementedError('a ragged batch keeps no dense CifHr map (no layout '
+                                          'is defined for one)')
+            h, w = ragged.h, ragged.w
+        else:
+            h, w = (cif.shape[3], cif.shape[4]) if heads is None else (heads.h, heads.w)
         cap = cap or default_ann_capacity(h, w)
         stages = STAGE_ALL | (STAGE_NMS_WIDE if self.density >= _B_FIRST_DENSITY else 0)
         while True:
-            if heads is None:
+            if ragged is not None:
+                b = self.launch_ragged(ragged, skeleton, cfg, cap=cap, stages=stages)
+            elif heads is None:
                 b = self.launch(cif, caf, skeleton, cfg, cap=cap, keep_cifhr=keep_cifhr,
                                 stages=stages, initial=initial)
             else:
@@ -279,15 +368,16 @@ class DecodeEngine:
         return b
 
     def decode(self, cif, caf, skeleton, cfg, cap=None, keep_cifhr=False, heads=None,
-               compact=None, initial=None):
+               compact=None, initial=None, ragged=None):
         """Full decode with overflow retry.  Returns (records, offsets, buffers).  With a
         HeadSet `heads`, cif / caf are ignored and the multi-scale decode runs.  `compact`
         flags (e.g. _abi.PACK_ALL) fetch compact records (pp_pack_compact) instead of full
         pp_ann records.  `initial` (InitialAnnotations): grown before the seed loop; the
-        buffers then hold out_index (see pp_decode_initial)."""
+        buffers then hold out_index (see pp_decode_initial).  `ragged` (RaggedFields): the
+        images decode at their own sizes (pp_decode_ragged); cif / caf are ignored."""
         b = self.launch_checked(cif, caf, skeleton, cfg, cap=cap, keep_cifhr=keep_cifhr,
-                                heads=heads, initial=initial)
-        k = cif.shape[1] if heads is None else heads.k
+                                heads=heads, initial=initial, ragged=ragged)
+        k = ragged.k if ragged is not None else cif.shape[1] if heads is None else heads.k
         recs, offsets = self.fetch(b, None if compact is None else
                                    (k, len(skeleton_array(skeleton)), compact))
         return recs, offsets, b

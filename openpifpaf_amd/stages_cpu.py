@@ -151,3 +151,56 @@ def decode_batch(cif, caf, skeleton, cfg, *, n_threads=0, cap=None):
     recs = np.concatenate([anns[i, :counts[i]] for i in range(n)]) if n else \
         np.zeros(0, ANN_DTYPE)
     return recs, offsets
+
+
+def pad_container(fields):
+    """Images' own fields [(n_fields, channels, h_i, w_i), ...] zero-padded on the right and
+    bottom into one float32 container (n, n_fields, channels, H, W) with (H, W) the largest
+    size, and the (n, 2) int32 extent table of the (h_i, w_i): what a ragged decode reads."""
+    fields = [_f32(f, 4, 'field') for f in fields]
+    if not fields:
+        raise ValueError('a ragged batch needs at least one image')
+    if any(f.shape[:2] != fields[0].shape[:2] for f in fields):
+        raise ValueError('the images of a ragged batch differ in fields or channels: ' +
+                         ', '.join(sorted({str(f.shape[:2]) for f in fields})))
+    ext = np.array([f.shape[2:] for f in fields], np.int32).reshape(-1, 2)
+    out = np.zeros((len(fields),) + fields[0].shape[:2] + tuple(ext.max(axis=0)), np.float32)
+    for i, f in enumerate(fields):
+        out[i, :, :, :f.shape[2], :f.shape[3]] = f
+    return out, ext
+
+
+def decode_ragged(cifs, cafs, skeleton, cfg, *, n_threads=0, cap=None):
+    """The decode of a ragged batch on host threads (pp_decode_ragged_cpu): cifs / cafs are
+    lists of the images' own fields, (K, 5, h_i, w_i) and (C, 9, h_i, w_i) with K and C the
+    same for every image -> (records, offsets) as decode_batch returns them.  Every image
+    decodes as it would alone at its own size; the annotation capacity starts from the
+    container's size and doubles until no image overflows."""
+    if len(cifs) != len(cafs):
+        raise ValueError('{} CIF fields for {} CAF fields'.format(len(cifs), len(cafs)))
+    cif, ext = pad_container(cifs)
+    caf, ext_caf = pad_container(cafs)
+    if cif.shape[2] != 5 or caf.shape[2] != 9:
+        raise ValueError('expected cif (K, 5, h, w) and caf (C, 9, h, w) per image')
+    if not np.array_equal(ext, ext_caf):
+        raise ValueError('cif and caf spatial shapes differ')
+    n, k, _, h, w = cif.shape
+    c = caf.shape[1]
+    sk = np.ascontiguousarray(skeleton, dtype=np.int32).reshape(-1, 2)
+    if len(sk) != c:
+        raise ValueError('skeleton has {} pairs for {} CAF fields'.format(len(sk), c))
+    cap = cap or int(min(8192, max(128, (h * w) // 8)))  # engine.default_ann_capacity
+    while True:
+        anns = np.zeros((n, cap), ANN_DTYPE)
+        counts = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        call('pp_decode_ragged_cpu', cif.ctypes.data, caf.ctypes.data, n, k, c, h, w,
+             ext.ctypes.data, sk.ctypes.data, ctypes.byref(cfg), anns.ctypes.data, cap,
+             counts.ctypes.data, status.ctypes.data, int(n_threads))
+        if not (status & PP_ST_ANN_OVERFLOW).any():
+            break
+        cap *= 2
+    if (status & PP_ST_DEC_OVERFLOW).any():
+        raise PPError('decoding/frontier order exceeded the record capacity')
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return np.concatenate([anns[i, :counts[i]] for i in range(n)]), offsets
