@@ -564,6 +564,50 @@ int pp_fields_from_conv_strided(const void *d_conv, int32_t conv_dtype,
                                 int32_t out_field0, void *stream);
 
 /*
+ * pp_fields_from_conv_ex for n_img images of different sizes, straight into the container of
+ * a ragged batch (see "Ragged batches" below) in one pass: inside image i's own field,
+ * [0, H_i) x [0, W_i) with (H_i, W_i) = (pp_fields_dim(h_i, quad), pp_fields_dim(w_i, quad)),
+ * every value is, bit for bit, what pp_fields_from_conv_ex gives for the dense
+ * (1, channels, h_i, w_i) copy of that image alone with the same conv_dtype, mirror, src_field
+ * and swap_ends (the mirror is about the image's own W_i); outside it the value is +0.  Every
+ * element of the written fields is stored exactly once: the container needs no memset, and
+ * its bytes are those of pp_fields_pack_ragged over the per-image ingests.
+ *   convs         HOST (n_img): device pointers to element (0, 0, 0) of each image's
+ *                 (channels, h_i, w_i) conv view; aligned to the element size, no more
+ *   conv_extents  HOST (n_img, 2): the conv sizes (h_i, w_i)
+ *   conv_strides  HOST (n_img, 2) or NULL: each image's channel and row strides in elements;
+ *                 NULL = every image dense.  The column stride is 1 (the planar class of
+ *                 pp_fields_from_conv_strided).  The row stride of an image with h_i = 1 is
+ *                 ignored.  Pointers and strides together describe a list of per-image
+ *                 tensors as well as a padded (n_img, channels, hmax, wmax) batch, or a
+ *                 channel slice of a fused one, with per-image valid extents.
+ *   d_container   (n_img, out_fields, 5 | 9 | 7, H, W) float32, 4-byte aligned; fields
+ *                 out_field0 .. out_field0 + n_fields - 1 of every image are written in full,
+ *                 the others are left alone
+ *   d_tables      pp_ragged_conv_tables_size(n_img) bytes, 8-byte aligned.  The three host
+ *                 tables are copied into it on the stream, the 8-byte entries first; pageable
+ *                 host tables are consumed before the call returns, pinned ones when the
+ *                 stream reaches the copy.  The kernel also writes the (n_img, 2) int32 FIELD
+ *                 extent table (H_i, W_i) that pp_decode_ragged takes, at d_tables +
+ *                 pp_ragged_conv_extents_offset(n_img) (the last 8 n_img bytes).
+ * Checked before any copy or launch: everything pp_fields_from_conv_ex checks; a NULL or
+ * misaligned conv pointer, a negative stride -> PP_EINVAL; a conv extent <= 0, a field extent
+ * larger than (H, W), H * W or n_img * out_fields * channels beyond int32, more than 65535
+ * images or fields (the launch grid) -> PP_ESHAPE; then, for n_img > 0, a table buffer too
+ * small -> PP_ENOMEM, d_tables not 8-byte or d_container not 4-byte aligned -> PP_EINVAL.
+ * n_img = 0 returns PP_OK after the checks.  Offsets are 64-bit.
+ */
+size_t pp_ragged_conv_tables_size(int32_t n_img);
+size_t pp_ragged_conv_extents_offset(int32_t n_img);
+int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
+                               const int32_t *conv_extents, const int64_t *conv_strides,
+                               int32_t n_img, int32_t n_fields, int32_t layout, int32_t quad,
+                               int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
+                               int32_t H, int32_t W, float *d_container, int32_t out_fields,
+                               int32_t out_field0, void *d_tables, size_t tables_bytes,
+                               void *stream);
+
+/*
  * nms.Keypoints.annotations (nms.py:17-57) over caller records, n_img independent groups:
  * d_anns (n_img, ann_capacity) with d_counts[i] records in group i (modified in place as
  * the reference modifies its Annotation objects: joints below keypoint_threshold zeroed,

@@ -114,6 +114,11 @@ _SIGNATURES = {
                                 _vp, _i32, _i32, _vp], ctypes.c_int),
     'pp_fields_from_conv_strided': ([_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                      _vp, _vp, _vp, _i32, _i32, _vp], ctypes.c_int),
+    # conv outputs of different sizes straight into a ragged batch's container
+    'pp_ragged_conv_tables_size': ([_i32], _sz),
+    'pp_ragged_conv_extents_offset': ([_i32], _sz),
+    'pp_fields_from_conv_ragged': ([_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                                    _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp], ctypes.c_int),
     'pp_nms_keypoints': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
                          ctypes.c_int),
     'pp_nms_keypoints_scored': ([_vp, _vp, _i32, _i32, _i32, _vp, _f64, _vp, _vp, _vp, _vp,

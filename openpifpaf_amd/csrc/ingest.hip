@@ -82,6 +82,41 @@ struct IngestStrides {
     int64_t img, ch, row, col;
 };
 
+// The index logic the three planar kernels share, for output pixel (X, Y) of output field f
+// inside a kernel<T, kEx> with IngestArgs a and IngestFlip t.  It is text, not a function:
+// as force-inlined functions the same lines compiled to other code in all twelve existing
+// instantiations, and the hflip ones ran 20 to 32 % slower (DESIGN.md §4 "Ragged ingest").
+//
+// PP_INGEST_PIXEL(W_own) declares the conv field fs, mirror / swap (the columns are mirrored
+// about W_own, the width of the image's own field; the CAF end points trade places) and the
+// conv pixel (y0, x0).  It undoes the dequads: T_q[c, Y, X] = T_{q-1}[4c + 2(Y&1) + (X&1),
+// Y>>1, X>>1], so the conv channel is mul * c + sub, mul = 4^quad, with the finest level's
+// offset the most significant.
+#define PP_INGEST_PIXEL(W_own)                                      \
+    int fs = f;                                                     \
+    bool mirror = false, swap = false;                              \
+    if (kEx) {                                                      \
+        mirror = t.mirror != 0;                                     \
+        if (t.has_src) fs = t.src_field[f];                         \
+        swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);     \
+    }                                                               \
+    int sub = 0, y0 = Y, x0 = mirror ? (W_own) - 1 - X : X, mul = 1; \
+    for (int q = 0; q < a.quad; q++) {                              \
+        sub = 4 * sub + (2 * (y0 & 1) + (x0 & 1));                  \
+        mul *= 4;                                                   \
+        y0 >>= 1;                                                   \
+        x0 >>= 1;                                                   \
+    }
+
+// PP_INGEST_CHANNEL(o) declares op and the conv channel ch that output channel o reads.  The
+// end points trade places in the regressions only (heads.py:209-212); CAF's four vector
+// components are exactly its ops 3 / 4.
+#define PP_INGEST_CHANNEL(o)                                \
+    const int op = a.op[o];                                 \
+    int comp = a.comp[o];                                   \
+    if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;     \
+    const int64_t ch = (int64_t)(a.grp_off[o] + fs * a.fld_mul[o] + comp) * mul + sub;
+
 template <typename T, bool kEx>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a, IngestFlip t) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -89,31 +124,11 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs a, IngestFlip t)
     const int f = blockIdx.y, img = blockIdx.z;
     if (pix >= HW) return;
     const int Y = (int)(pix / a.W), X = (int)(pix % a.W);
-    int fs = f;
-    bool mirror = false, swap = false;
-    if (kEx) {
-        mirror = t.mirror != 0;
-        if (t.has_src) fs = t.src_field[f];
-        swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);
-    }
-    // undo the dequads: T_q[c, Y, X] = T_{q-1}[4c + 2(Y&1) + (X&1), Y>>1, X>>1], so the
-    // conv channel is 4^quad * c + sub with the finest level's offset the most significant
-    int sub = 0, y0 = Y, x0 = mirror ? a.W - 1 - X : X, mul = 1;
-    for (int q = 0; q < a.quad; q++) {
-        sub = 4 * sub + (2 * (y0 & 1) + (x0 & 1));
-        mul *= 4;
-        y0 >>= 1;
-        x0 >>= 1;
-    }
+    PP_INGEST_PIXEL(a.W)
     const T *src = (const T *)a.conv + (int64_t)img * a.conv_ch * a.h * a.w + (int64_t)y0 * a.w + x0;
     float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW + pix;
     for (int o = 0; o < a.n_out; o++) {
-        const int op = a.op[o];
-        int comp = a.comp[o];
-        // the end points trade places in the regressions only (heads.py:209-212); CAF's
-        // four vector components are exactly its ops 3 / 4
-        if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
-        const int64_t ch = (int64_t)(a.grp_off[o] + fs * a.fld_mul[o] + comp) * mul + sub;
+        PP_INGEST_CHANNEL(o)
         const float v = load_f32(src + ch * a.h * a.w);
         dst[(int64_t)o * HW] = ingest_value(op, v, mirror, X, Y);
     }
@@ -128,35 +143,69 @@ __global__ __launch_bounds__(256) void ingest_strided_kernel(IngestArgs a, Inges
     const int f = blockIdx.y, img = blockIdx.z;
     if (pix >= HW) return;
     const int Y = (int)(pix / a.W), X = (int)(pix % a.W);
-    int fs = f;
-    bool mirror = false, swap = false;
-    if (kEx) {
-        mirror = t.mirror != 0;
-        if (t.has_src) fs = t.src_field[f];
-        swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);
-    }
-    // undo the dequads: T_q[c, Y, X] = T_{q-1}[4c + 2(Y&1) + (X&1), Y>>1, X>>1], so the
-    // conv channel is 4^quad * c + sub with the finest level's offset the most significant
-    int sub = 0, y0 = Y, x0 = mirror ? a.W - 1 - X : X, mul = 1;
-    for (int q = 0; q < a.quad; q++) {
-        sub = 4 * sub + (2 * (y0 & 1) + (x0 & 1));
-        mul *= 4;
-        y0 >>= 1;
-        x0 >>= 1;
-    }
+    PP_INGEST_PIXEL(a.W)
     const T *src = (const T *)a.conv + (int64_t)img * s.img + (int64_t)y0 * s.row + x0;
     float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW + pix;
     for (int o = 0; o < a.n_out; o++) {
-        const int op = a.op[o];
-        int comp = a.comp[o];
-        // the end points trade places in the regressions only (heads.py:209-212); CAF's
-        // four vector components are exactly its ops 3 / 4
-        if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
-        const int64_t ch = (int64_t)(a.grp_off[o] + fs * a.fld_mul[o] + comp) * mul + sub;
+        PP_INGEST_CHANNEL(o)
         const float v = load_f32(src + ch * s.ch);
         dst[(int64_t)o * HW] = ingest_value(op, v, mirror, X, Y);
     }
 }
+
+// ---- n images of their own sizes into one container (pp_fields_from_conv_ragged) ----
+//
+// The device tables, staged from the caller's host tables: per image the pointer to element
+// (0, 0, 0) of its conv view, its channel and row strides (strides NULL: every image dense)
+// and its conv extents.  field_ext is written here, the (H_i, W_i) pp_decode_ragged reads.
+struct IngestRagged {
+    const void *const *conv;  // (n)
+    const int64_t *strides;   // (n, 2) channel, row; or NULL
+    const int32_t *conv_ext;  // (n, 2) h_i, w_i
+    int32_t *field_ext;       // (n, 2) H_i, W_i
+};
+
+// ingest_strided_kernel's work unit over the CONTAINER's pixels (a.H, a.W; a.h, a.w and
+// a.conv are unused): inside the image's own field the ingested value, mirrored about the
+// image's own width, outside it +0, every element of the written fields stored exactly
+// once.  The image is blockIdx.z, so its table entries are scalar loads.
+template <typename T, bool kEx>
+__global__ __launch_bounds__(256) void ingest_ragged_kernel(IngestArgs a, IngestFlip t,
+                                                            IngestRagged r) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t HW = (int64_t)a.H * a.W;
+    const int f = blockIdx.y, img = blockIdx.z;
+    const int h = r.conv_ext[2 * img], w = r.conv_ext[2 * img + 1];
+    int Hi = h, Wi = w;
+    for (int q = 0; q < a.quad; q++) {  // pp_fields_dim
+        Hi = 2 * Hi - 1;
+        Wi = 2 * Wi - 1;
+    }
+    if (blockIdx.x == 0 && f == 0 && threadIdx.x == 0) {
+        r.field_ext[2 * img] = Hi;
+        r.field_ext[2 * img + 1] = Wi;
+    }
+    if (pix >= HW) return;
+    const int Y = (int)(pix / a.W), X = (int)(pix % a.W);
+    float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW + pix;
+    if (Y >= Hi || X >= Wi) {
+        for (int o = 0; o < a.n_out; o++) dst[(int64_t)o * HW] = 0.0f;
+        return;
+    }
+    const int64_t s_ch = r.strides ? r.strides[2 * img] : (int64_t)h * w;
+    const int64_t s_row = r.strides ? r.strides[2 * img + 1] : (int64_t)w;
+    PP_INGEST_PIXEL(Wi)
+    // a stride whose extent is 1 meets index 0 only (h = 1: y0 = 0)
+    const T *src = (const T *)r.conv[img] + (int64_t)y0 * s_row + x0;
+    for (int o = 0; o < a.n_out; o++) {
+        PP_INGEST_CHANNEL(o)
+        const float v = load_f32(src + ch * s_ch);
+        dst[(int64_t)o * HW] = ingest_value(op, v, mirror, X, Y);
+    }
+}
+
+#undef PP_INGEST_PIXEL
+#undef PP_INGEST_CHANNEL
 
 // ---- channels adjacent in memory (channels-last and its slices) ----
 //
@@ -327,6 +376,17 @@ static void launch_ingest(Route route, const IngestArgs &a, const IngestFlip &t,
                            t, s, g);
 }
 
+template <typename T>
+static void launch_ingest_ragged(const IngestArgs &a, const IngestFlip &t, const IngestRagged &r,
+                                 bool ex, hipStream_t stream) {
+    const int64_t HW = (int64_t)a.H * a.W;
+    const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)a.n_fields, (unsigned)a.n_img);
+    if (ex)
+        hipLaunchKernelGGL((ingest_ragged_kernel<T, true>), grid, dim3(256), 0, stream, a, t, r);
+    else
+        hipLaunchKernelGGL((ingest_ragged_kernel<T, false>), grid, dim3(256), 0, stream, a, t, r);
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -338,18 +398,12 @@ int64_t pp_fields_dim(int64_t n, int32_t quad) {
     return n;
 }
 
-// conv_strides NULL: the dense (n_img, channels, h, w) tensor of the two older symbols
-static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dtype,
-                            const int64_t *conv_strides, int32_t n_img, int32_t n_fields, int32_t layout, int32_t h,
-                            int32_t w, int32_t quad, int32_t mirror, const int32_t *src_field,
-                            const uint8_t *swap_ends, float *d_out, int32_t out_fields,
-                            int32_t out_field0, void *stream) {
-    const std::string name(who);
-    if (!d_conv || !d_out) return fail(PP_EINVAL, name + ": NULL argument");
-    if (n_img < 0 || n_fields <= 0 || h <= 0 || w <= 0 || quad < 0 || quad > 4)
-        return fail(PP_ESHAPE, name + ": bad shape");
-    IngestArgs a{};
-    IngestFlip t{};
+// The checks every ingest symbol shares after its NULL and shape checks, and the kernel
+// arguments that do not depend on the images' sizes or addresses (n_fields > 0, 0 <= quad <= 4).
+static int ingest_setup(const std::string &name, int32_t conv_dtype, int32_t n_fields,
+                        int32_t layout, int32_t quad, int32_t mirror, const int32_t *src_field,
+                        const uint8_t *swap_ends, int32_t out_fields, int32_t out_field0,
+                        IngestArgs &a, IngestFlip &t) {
     // (n_confidences, n_vectors, n_scales) of IntensityMeta / AssociationMeta /
     // DetectionMeta (heads.py:218-265) and the collector's output channel order
     static const int metas[3][3] = {{1, 1, 1}, {1, 2, 2}, {1, 2, 0}};
@@ -380,15 +434,8 @@ static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dt
         for (int f = 0; f < n_fields; f++)
             if (swap_ends[f]) t.swap_mask |= (uint64_t)1 << f;
     t.mirror = mirror != 0;
-    a.conv = d_conv;
-    a.out = d_out;
-    a.n_img = n_img;
     a.n_fields = n_fields;
-    a.h = h;
-    a.w = w;
     a.quad = quad;
-    a.H = (int)pp_fields_dim(h, quad);
-    a.W = (int)pp_fields_dim(w, quad);
     a.n_conf = metas[layout][0];
     a.n_vec = metas[layout][1];
     a.n_scales = metas[layout][2];
@@ -425,6 +472,31 @@ static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dt
             a.op[o] = 2;
         }
     }
+    return PP_OK;
+}
+
+// conv_strides NULL: the dense (n_img, channels, h, w) tensor of the two older symbols
+static int fields_from_conv(const char *who, const void *d_conv, int32_t conv_dtype,
+                            const int64_t *conv_strides, int32_t n_img, int32_t n_fields, int32_t layout, int32_t h,
+                            int32_t w, int32_t quad, int32_t mirror, const int32_t *src_field,
+                            const uint8_t *swap_ends, float *d_out, int32_t out_fields,
+                            int32_t out_field0, void *stream) {
+    const std::string name(who);
+    if (!d_conv || !d_out) return fail(PP_EINVAL, name + ": NULL argument");
+    if (n_img < 0 || n_fields <= 0 || h <= 0 || w <= 0 || quad < 0 || quad > 4)
+        return fail(PP_ESHAPE, name + ": bad shape");
+    IngestArgs a{};
+    IngestFlip t{};
+    if (const int rc = ingest_setup(name, conv_dtype, n_fields, layout, quad, mirror, src_field,
+                                    swap_ends, out_fields, out_field0, a, t))
+        return rc;
+    a.conv = d_conv;
+    a.out = d_out;
+    a.n_img = n_img;
+    a.h = h;
+    a.w = w;
+    a.H = (int)pp_fields_dim(h, quad);
+    a.W = (int)pp_fields_dim(w, quad);
     // the plain f32 ingest keeps its own instantiation without the table reads
     const bool ex = t.mirror || t.has_src || t.swap_mask;
     Route route = kDense;
@@ -499,6 +571,94 @@ int pp_fields_from_conv(const float *d_conv, int32_t n_img, int32_t n_fields, in
                         int32_t h, int32_t w, int32_t quad, float *d_out, void *stream) {
     return fields_from_conv("pp_fields_from_conv", d_conv, PP_DTYPE_F32, nullptr, n_img, n_fields,
                             layout, h, w, quad, 0, nullptr, nullptr, d_out, n_fields, 0, stream);
+}
+
+// d_tables: the pointers (8 n bytes), the strides (16 n), the conv extents (8 n) and the field
+// extents (8 n) the kernel writes
+size_t pp_ragged_conv_tables_size(int32_t n_img) {
+    return n_img > 0 ? (size_t)n_img * (sizeof(void *) + 2 * sizeof(int64_t) + 4 * sizeof(int32_t))
+                     : 0;
+}
+
+size_t pp_ragged_conv_extents_offset(int32_t n_img) {
+    return n_img > 0 ? (size_t)n_img * (sizeof(void *) + 2 * sizeof(int64_t) + 2 * sizeof(int32_t))
+                     : 0;
+}
+
+int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
+                               const int32_t *conv_extents, const int64_t *conv_strides,
+                               int32_t n_img, int32_t n_fields, int32_t layout, int32_t quad,
+                               int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
+                               int32_t H, int32_t W, float *d_container, int32_t out_fields,
+                               int32_t out_field0, void *d_tables, size_t tables_bytes,
+                               void *stream) {
+    const std::string name("pp_fields_from_conv_ragged");
+    if (!convs || !conv_extents || !d_container || !d_tables)
+        return fail(PP_EINVAL, name + ": NULL argument");
+    if (n_img < 0 || n_fields <= 0 || H <= 0 || W <= 0 || quad < 0 || quad > 4)
+        return fail(PP_ESHAPE, name + ": bad shape");
+    IngestArgs a{};
+    IngestFlip t{};
+    if (const int rc = ingest_setup(name, conv_dtype, n_fields, layout, quad, mirror, src_field,
+                                    swap_ends, out_fields, out_field0, a, t))
+        return rc;
+    if ((int64_t)H * W > INT32_MAX || (int64_t)out_fields * a.n_out > INT32_MAX ||
+        (int64_t)n_img * out_fields * a.n_out > INT32_MAX)
+        return fail(PP_ESHAPE, name + ": bad shape (a product beyond int32)");
+    if (n_img > 65535 || n_fields > 65535)
+        return fail(PP_ESHAPE, name + ": more than 65535 images or fields (the launch grid)");
+    const uintptr_t elem = conv_dtype == PP_DTYPE_F32 ? 4 : 2;
+    for (int i = 0; i < n_img; i++) {
+        if (!convs[i]) return fail(PP_EINVAL, name + ": NULL conv pointer");
+        if ((uintptr_t)convs[i] & (elem - 1))
+            return fail(PP_EINVAL, name + ": misaligned conv pointer");
+        const int32_t h = conv_extents[2 * i], w = conv_extents[2 * i + 1];
+        if (h <= 0 || w <= 0) return fail(PP_ESHAPE, name + ": conv extent <= 0");
+        if (pp_fields_dim(h, quad) > H || pp_fields_dim(w, quad) > W)
+            return fail(PP_ESHAPE, name + ": field extent outside the container");
+        // the stride of a dimension of extent 1 says nothing (the channels are never 1)
+        if (conv_strides && (conv_strides[2 * i] < 0 || (h > 1 && conv_strides[2 * i + 1] < 0)))
+            return fail(PP_EINVAL, name + ": negative conv stride");
+    }
+    if (n_img == 0) return PP_OK;
+    if (tables_bytes < pp_ragged_conv_tables_size(n_img))
+        return fail(PP_ENOMEM, name + ": table buffer too small");
+    if (((uintptr_t)d_tables & 7u) || ((uintptr_t)d_container & 3u))
+        return fail(PP_EINVAL, name + ": misaligned buffer");
+    const hipStream_t s = (hipStream_t)stream;
+    char *tab = (char *)d_tables;
+    const size_t n = (size_t)n_img, str_off = n * sizeof(void *),
+                 cext_off = str_off + n * 2 * sizeof(int64_t);
+    // straight from the caller's tables: pageable ones are consumed before these return (the
+    // runtime waits for the copy); pinned ones are read when the stream gets there and must
+    // stay valid until then
+    bool ok = hipMemcpyAsync(tab, convs, n * sizeof(void *), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok && conv_strides)
+        ok = hipMemcpyAsync(tab + str_off, conv_strides, n * 2 * sizeof(int64_t),
+                            hipMemcpyHostToDevice, s) == hipSuccess;
+    ok = ok && hipMemcpyAsync(tab + cext_off, conv_extents, n * 2 * sizeof(int32_t),
+                              hipMemcpyHostToDevice, s) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(PP_EHIP, name + ": staging the tables failed");
+    }
+    a.out = d_container;
+    a.n_img = n_img;
+    a.H = H;
+    a.W = W;
+    IngestRagged r{};
+    r.conv = (const void *const *)tab;
+    r.strides = conv_strides ? (const int64_t *)(tab + str_off) : nullptr;
+    r.conv_ext = (const int32_t *)(tab + cext_off);
+    r.field_ext = (int32_t *)(tab + pp_ragged_conv_extents_offset(n_img));
+    const bool ex = t.mirror || t.has_src || t.swap_mask;
+    if (conv_dtype == PP_DTYPE_F32)
+        launch_ingest_ragged<float>(a, t, r, ex, s);
+    else if (conv_dtype == PP_DTYPE_F16)
+        launch_ingest_ragged<__half>(a, t, r, ex, s);
+    else
+        launch_ingest_ragged<Bf16>(a, t, r, ex, s);
+    return check_launch("pp_fields_from_conv_ragged");
 }
 
 }  // extern "C"

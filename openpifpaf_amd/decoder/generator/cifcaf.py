@@ -285,6 +285,8 @@ class CifCaf(Generator):
         if not self.field_config.is_single_scale():
             raise NotImplementedError('a ragged batch needs a single-scale FieldConfig (one '
                                       'CIF and one CAF head); multi-scale heads are not built')
+        if isinstance(fields_list, RaggedFields):  # packed or ingested already
+            return fields_list
         cif_i, caf_i, _ = self.field_config.single_scale()
         return RaggedFields([(_device.to_device(f[cif_i]), _device.to_device(f[caf_i]))
                              for f in fields_list])
@@ -293,7 +295,9 @@ class CifCaf(Generator):
         """One entry per image, each image's head outputs [cif (K, 5, h_i, w_i), caf (C, 9,
         h_i, w_i), ...] at its OWN size (what Generator.fields_batch returns, from any
         number of forward passes) -> one list of Annotation per image, each as __call__
-        gives it for that image alone, decoded as one device batch (pp_decode_ragged)."""
+        gives it for that image alone, decoded as one device batch (pp_decode_ragged).  An
+        engine.RaggedFields (e.g. RaggedFields.from_conv, heads.RaggedCollector) in place of
+        the list is decoded as it is."""
         ragged = self._ragged(fields_list, kw)
         recs, offsets, _ = engine().decode(None, None, skeleton_array(self.skeleton),
                                            self.config(), compact=PACK_ALL, ragged=ragged)

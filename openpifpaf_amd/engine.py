@@ -163,7 +163,9 @@ class RaggedFields:
     into the containers `cif` (n, K, 5, H, W) and `caf` (n, C, 9, H, W), (H, W) the largest
     size, zero outside each image's extent, and owns them with the extent table (`extents`,
     device (n, 2) int32; `extents_host` the same on the host).  The images' tensors may be
-    freed once the pack has run.  A list of equal shapes takes the same route."""
+    freed once the pack has run.  A list of equal shapes takes the same route.
+    RaggedFields.from_conv builds the same object from the heads' conv outputs, without
+    per-image fields and without the pack."""
 
     def __init__(self, fields):
         lib = load()
@@ -201,9 +203,51 @@ class RaggedFields:
         self.extents = self._tables[0][ext_off:].view(torch.int32).view(n, 2)
         self.pack()
 
+    _ingests = ()  # from_conv: the heads.RaggedIngest of each head, CIF first
+
+    @classmethod
+    def from_conv(cls, cif_convs, caf_convs, n_cif, n_caf, quad=1, conv_extents=None,
+                  cif_hflip=None, caf_hflip=None, caf_parts=None):
+        """The same object from the heads' conv outputs, one HIP pass per head straight into
+        the containers (heads.fields_from_conv_ragged has the forms `cif_convs` / `caf_convs`
+        and `conv_extents` take): no per-image fields and no pack.  `caf_parts`, a list of
+        (convs, n_fields, hflip), replaces caf_convs / n_caf / caf_hflip: the parts are
+        written side by side into one CAF container (CAF and dense CAF of the
+        dense-connection layout).  pack() runs the ingest launches again."""
+        from .heads import RaggedIngest  # pylint: disable=import-outside-toplevel
+        if caf_parts is None:
+            caf_parts = [(caf_convs, n_caf, caf_hflip)]
+        heads = [cif_convs] + [p[0] for p in caf_parts]
+        sizes = {len(c) for c in heads}
+        if len(sizes) != 1:
+            raise ValueError('the heads of a ragged batch have different numbers of images: ' +
+                             ', '.join(str(s) for s in sorted(sizes)))
+        cif = RaggedIngest(cif_convs, n_cif, 'cif', quad, cif_hflip, conv_extents)
+        total, parts = sum(p[1] for p in caf_parts), []
+        for convs, n_fields, hflip in caf_parts:
+            done = sum(p[1] for p in caf_parts[:len(parts)])
+            parts.append(RaggedIngest(convs, n_fields, 'caf', quad, hflip, conv_extents,
+                                      shape=(cif.h, cif.w) if not parts else None,
+                                      out=parts[0].out if parts else None, out_field0=done,
+                                      out_fields=total))
+        if any(not np.array_equal(p.extents_host, cif.extents_host) for p in parts):
+            raise ValueError('the CIF and CAF conv outputs of a ragged batch differ in size')
+        self = cls.__new__(cls)
+        self.n, self.k, self.c, self.h, self.w = cif.n, n_cif, total, cif.h, cif.w
+        self.cif, self.caf = cif.out, parts[0].out
+        self.extents, self.extents_host = cif.extents, cif.extents_host
+        self._ingests = [cif] + parts
+        self.pack()
+        return self
+
     def pack(self):
         """The two pack launches (CIF, then CAF) on the current stream, from the tables built
-        at construction: again after the images' tensors were rewritten in place."""
+        at construction: again after the images' tensors were rewritten in place.  After
+        from_conv: the ingest launches."""
+        for ingest in self._ingests:
+            ingest.launch()
+        if self._ingests:
+            return
         size, ext_off = self._host.shape[1], load().pp_ragged_extents_offset(self.n)
         for kind, (out, planes, ch) in enumerate(((self.cif, self.k, 5), (self.caf, self.c, 9))):
             call('pp_fields_pack_ragged', ctypes.c_void_p(self._host[kind].data_ptr()),

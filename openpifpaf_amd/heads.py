@@ -12,9 +12,12 @@ Channels-last tensors and channel, batch or spatial slices of a larger tensor ar
 they lie, by their strides (pp_fields_from_conv_strided).
 `MultiScaleCollector` does that for the head list of a ShellMultiScale-style model
 (network/nets.py:95-143), whose second five scales come from the mirrored image.
+`fields_from_conv_ragged` / `RaggedCollector` ingest the conv outputs of images of different
+sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged).
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _device, constants
@@ -123,6 +126,195 @@ def fields_from_conv(conv, n_fields, kind, quad=1, hflip=None, out=None, out_fie
          int(hflip is not None), src_field, swap_ends, _device.ptr(out), out.shape[1],
          int(out_field0), _device.stream())
     return out
+
+
+class RaggedIngest:
+    """One head's conv outputs of n images of different sizes and the container of a ragged
+    batch they are ingested into (pp_fields_from_conv_ragged): the pinned host tables, the
+    device tables and the output, built once; launch() enqueues the pass on the current
+    stream, again after the conv tensors were rewritten in place.  The arguments are
+    fields_from_conv_ragged's; `out_fields` widens a container allocated here.
+
+    out           the container (n, out_fields, 5 | 9 | 7, H, W)
+    extents       device (n, 2) int32 field sizes (H_i, W_i), written by the launch
+    extents_host  the same table, NumPy"""
+
+    def __init__(self, convs, n_fields, kind, quad=1, hflip=None, conv_extents=None,
+                 shape=None, out=None, out_field0=0, out_fields=None):
+        layout, n_out = LAYOUTS[kind]
+        channels = n_fields * n_out * 4 ** quad
+        if isinstance(convs, torch.Tensor):
+            ptrs, strides, ext, keep = self._batched(convs, conv_extents)
+        else:
+            if conv_extents is not None:
+                raise ValueError('conv_extents goes with one batched tensor; the tensors of a '
+                                 'list have their own sizes')
+            ptrs, strides, ext, keep = self._listed(list(convs))
+        first = keep[0]
+        if first.shape[-3] != channels:
+            raise ValueError('{} conv expects {} channels, got {}'.format(
+                kind, channels, first.shape[-3]))
+        self._convs = keep  # the tables point into them
+        self.n = n = len(ext)
+        self.extents_host = ext.astype(np.int32)
+        for _ in range(quad):  # pp_fields_dim
+            self.extents_host = 2 * self.extents_host - 1
+        largest = tuple(int(v) for v in self.extents_host.max(axis=0))
+        if out is not None and shape is None:
+            shape = tuple(out.shape[3:])
+        self.h, self.w = (int(v) for v in shape) if shape is not None else largest
+        if self.h < largest[0] or self.w < largest[1]:
+            raise ValueError('a container of {} x {} does not hold fields of {} x {}'.format(
+                self.h, self.w, *largest))
+        if out is None:
+            if out_field0 and out_fields is None:
+                raise ValueError('out_field0 needs out')
+            out = torch.empty((n, out_fields or n_fields, n_out, self.h, self.w),
+                              dtype=torch.float32, device=first.device)
+        elif (not _device.is_device(out) or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.dim() != 5 or out.device != first.device
+              or (out.shape[0],) + tuple(out.shape[2:]) != (n, n_out, self.h, self.w)):
+            raise ValueError('out must be a contiguous float32 device tensor (n, out_fields, '
+                             '{}, H, W) for these convs'.format(n_out))
+        if out_field0 < 0 or out_field0 + n_fields > out.shape[1]:
+            raise ValueError('fields {}..{} do not fit in the {} of out'.format(
+                out_field0, out_field0 + n_fields - 1, out.shape[1]))
+        self.out, self.out_field0 = out, int(out_field0)
+        self._src_field, self._swap_ends = (hflip.tables(n_fields) if hflip is not None
+                                            else (None, None))
+        self._args = (_DTYPES[first.dtype], n_fields, layout, quad, int(hflip is not None))
+        # one pinned host block: pointers, strides, conv extents (8-byte entries first)
+        lib = load()
+        self._host = torch.empty(32 * n, dtype=torch.uint8, pin_memory=True)
+        host = self._host.numpy()
+        host[:8 * n].view(np.uint64)[:] = ptrs
+        host[8 * n:24 * n].view(np.int64)[:] = strides.reshape(-1)
+        host[24 * n:].view(np.int32)[:] = ext.reshape(-1)
+        size, ext_off = lib.pp_ragged_conv_tables_size(n), lib.pp_ragged_conv_extents_offset(n)
+        self._tables = torch.empty(size, dtype=torch.uint8, device=first.device)
+        self.extents = self._tables[ext_off:].view(torch.int32).view(n, 2)
+
+    @staticmethod
+    def _check(t):
+        if not (_device.is_device(t) and t.dtype in _DTYPES):
+            raise ValueError('ragged conv outputs must be float32, float16 or bfloat16 device '
+                             'tensors')
+
+    @classmethod
+    def _listed(cls, convs):
+        """Per-image tensors (ch, h_i, w_i) or (1, ch, h_i, w_i): a view whose columns are not
+        adjacent (channels-last included) is copied, that image only."""
+        if not convs:
+            raise ValueError('a ragged batch needs at least one image')
+        keep = []
+        for t in convs:
+            cls._check(t)
+            if t.dim() == 4 and t.shape[0] == 1:
+                t = t[0]
+            if t.dim() != 3:
+                raise ValueError('expected per-image conv outputs (ch, h, w) or (1, ch, h, w), '
+                                 'got {}'.format(tuple(t.shape)))
+            if t.shape[2] > 1 and t.stride(2) != 1:
+                t = t.contiguous()
+            keep.append(t)
+        if any(t.dtype != keep[0].dtype or t.device != keep[0].device or
+               t.shape[0] != keep[0].shape[0] for t in keep):
+            raise ValueError('the conv outputs of a ragged batch differ in type, device or '
+                             'channels')
+        ptrs = np.array([t.data_ptr() for t in keep], np.uint64)
+        strides = np.array([t.stride()[:2] for t in keep], np.int64)
+        ext = np.array([t.shape[1:] for t in keep], np.int64)
+        return ptrs, strides, ext, keep
+
+    @classmethod
+    def _batched(cls, conv, conv_extents):
+        """One (n, ch, hmax, wmax) tensor whose image i is valid in [0, h_i) x [0, w_i):
+        pointers are base + i * image stride (no per-image data_ptr())."""
+        cls._check(conv)
+        if conv.dim() != 4 or conv.shape[0] == 0:
+            raise ValueError('expected a batched conv output (n, ch, hmax, wmax), n > 0')
+        n = conv.shape[0]
+        if conv_extents is None:
+            ext = np.tile(np.array(conv.shape[2:], np.int64), (n, 1))
+        else:
+            ext = np.asarray(conv_extents, dtype=np.int64)
+        if ext.shape != (n, 2) or (ext <= 0).any() or (ext > np.array(conv.shape[2:])).any():
+            raise ValueError('conv_extents must be (n, 2) rows (h_i, w_i) inside the batched '
+                             'tensor, 0 < h_i <= {}, 0 < w_i <= {}'.format(*conv.shape[2:]))
+        if conv.shape[3] > 1 and conv.stride(3) != 1:
+            conv = conv.contiguous()
+        ptrs = (np.uint64(conv.data_ptr()) + np.arange(n, dtype=np.uint64) *
+                np.uint64(conv.stride(0) * conv.element_size()))
+        strides = np.tile(np.array(conv.stride()[1:3], np.int64), (n, 1))
+        return ptrs, strides, ext, [conv]
+
+    def launch(self):
+        self.enqueue()
+        _hold(self)
+        return self
+
+    def enqueue(self):
+        """The library call alone; the caller keeps this object until the stream is past it."""
+        n, size = self.n, self._tables.numel()
+        dtype, n_fields, layout, quad, mirror = self._args
+        host = self._host.data_ptr()
+        call('pp_fields_from_conv_ragged', ctypes.c_void_p(host), dtype,
+             ctypes.c_void_p(host + 24 * n), ctypes.c_void_p(host + 8 * n), n, n_fields, layout,
+             quad, mirror, self._src_field, self._swap_ends, self.h, self.w,
+             _device.ptr(self.out), self.out.shape[1], self.out_field0,
+             _device.ptr(self._tables), ctypes.c_size_t(size), _device.stream())
+
+
+# launches whose pinned host tables and conv tensors the stream may not have read yet: they
+# stay referenced until an event recorded behind the launch has passed, whatever the caller
+# keeps of the results
+_PENDING = []
+
+
+def _hold(ingest):
+    _PENDING[:] = [(e, i) for e, i in _PENDING if not e.query()]
+    event = torch.cuda.Event()
+    event.record()
+    _PENDING.append((event, ingest))
+
+
+def fields_from_conv_ragged(convs, n_fields, kind, quad=1, hflip=None, conv_extents=None,
+                            shape=None, out=None, out_field0=0):
+    """Conv outputs of n images of different sizes -> the container of a ragged batch
+    (engine.RaggedFields, CifCaf.decode_ragged) in one HIP pass per head
+    (pp_fields_from_conv_ragged): no per-image fields and no pack.
+
+    `convs` is a list of per-image device tensors (ch, h_i, w_i) or (1, ch, h_i, w_i), or one
+    (n, ch, hmax, wmax) tensor with `conv_extents` (n, 2), the valid (h_i, w_i) of each image
+    (a padded batch, or a channel slice of a fused one).  float32, float16 and bfloat16 are
+    read as they lie, by their channel and row strides; a view whose columns are not adjacent
+    (channels-last included) is copied once with .contiguous(), for a list that image only.
+    `hflip` as in fields_from_conv; the mirror is about each image's own width.  `shape`
+    (H, W) sets a container larger than the largest field size, which is the default.  With
+    `out` (n, out_fields, 5 | 9 | 7, H, W) the fields go to out[:, out_field0:out_field0 +
+    n_fields], written in full (zero outside each image's extent), the rest is left alone.
+
+    Returns (container, device (n, 2) int32 table of the field sizes (H_i, W_i), the same
+    table on the host)."""
+    ing = RaggedIngest(convs, n_fields, kind, quad, hflip, conv_extents, shape, out,
+                       out_field0).launch()
+    return ing.out, ing.extents, ing.extents_host
+
+
+class RaggedCollector(torch.nn.Module):
+    """CifCafCollector for images of different sizes: forward((cif_convs, caf_convs),
+    conv_extents=None) -> engine.RaggedFields, each head ingested straight into its
+    container (the arguments are RaggedFields.from_conv's)."""
+
+    def __init__(self, n_cif, n_caf, quad=1):
+        super().__init__()
+        self.n_cif, self.n_caf, self.quad = n_cif, n_caf, quad
+
+    def forward(self, *args, conv_extents=None):  # pylint: disable=arguments-differ
+        from .engine import RaggedFields  # pylint: disable=import-outside-toplevel
+        cif_convs, caf_convs = args[0]
+        return RaggedFields.from_conv(cif_convs, caf_convs, self.n_cif, self.n_caf, self.quad,
+                                      conv_extents=conv_extents)
 
 
 class CifCafCollector(torch.nn.Module):
