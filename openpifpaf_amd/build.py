@@ -23,12 +23,14 @@ CFLAGS = [
 ]
 
 
-# per-file flags: splat.hip's fold gains nothing from packed f32; without the SLP vectorizer
+# per-file flags: cifhr.hip's fold gains nothing from packed f32; without the SLP vectorizer
 # the uniform CifHr runs 2-3 % faster (dense 5.41 -> 5.31 ms, sparse 4.36 -> 4.14-4.25 ms per
 # 256 images, A/B on one box).  Hand-written packed folds measured slower too (dense uniform
 # 5.48 -> 5.86-5.99 ms, profiles/r05p_fold_packed_ab.txt), although an isolated stream of
-# v_pk_fma_f32 runs 1.6-1.9x the element rate of v_fma_f32 (tools/ubench/pk_rate.hip)
-FILE_FLAGS = {'splat.hip': ['-fno-slp-vectorize']}
+# v_pk_fma_f32 runs 1.6-1.9x the element rate of v_fma_f32 (tools/ubench/pk_rate.hip).
+# splat.hip held the CifHr kernels when this was measured; the primitives that stayed in it
+# keep the flag they were built with
+FILE_FLAGS = {'cifhr.hip': ['-fno-slp-vectorize'], 'splat.hip': ['-fno-slp-vectorize']}
 
 
 VARIANTS = {
@@ -92,7 +94,7 @@ def build(force=False, verbose=True, variant=''):
         return lib
     # the diagnostic variant (never loaded by default): 'stamps' (in-kernel cycle stamps)
     extra = VARIANTS.get(variant, [])
-    # the largest sources start first (the seed loops, splat.hip and stages.hip take longest:
+    # the largest sources start first (the seed loops, cifhr.hip and stages.hip take longest:
     # none of them waits in the pool behind small files); the link keeps the order by name
     queue = sorted(sources(), key=os.path.getsize, reverse=True)
     with concurrent.futures.ThreadPoolExecutor(min(8, len(queue))) as ex:

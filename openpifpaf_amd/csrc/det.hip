@@ -1,6 +1,6 @@
 // det.hip — the CifDet detection decoder (decoder/generator/cifdet.py:27-52) on gfx950.
 //
-//   pp_cifdet_hr (splat.hip)   CifDetHr: the CifHr gather-fold with detection sigmas
+//   pp_cifdet_hr (cifhr.hip)   CifDetHr: the CifHr gather-fold with detection sigmas
 //   det_seeds_emit_kernel      CifDetSeeds.fill_cif (cif_seeds.py:67-90) per (image, field)
 //   det_select_kernel          per (image, field): the field's seeds sorted as the reference
 //                              orders them, then the occupancy loop of cifdet.py:38-45.

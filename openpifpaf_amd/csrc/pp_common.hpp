@@ -27,6 +27,8 @@ int fail(int status, const std::string &msg);
 int check_launch(const char *what);
 
 inline int64_t hr_dim(int64_t n, int stride) { return (n - 1) * stride + 1; }
+// a rounded up to a multiple of b (workspace offsets, pitches, grid sizes)
+inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 // CifHr maps must stay below this many pixels per side: the fold packs a pixel's (x, y)
 // into two signed 16-bit halves for its box test
 constexpr int kMaxHrSide = 32768;
@@ -488,7 +490,7 @@ int make_heads(const pp_scale *sc, int n, int pairs, int need, Heads *h, const c
 // one CIF and one CAF head from the single-scale arguments
 Heads single_head(const float *cif, const float *caf, int H, int W, int stride);
 
-// stage launchers over heads (splat.hip, stages.hip)
+// stage launchers over heads (cifhr.hip, stages.hip)
 size_t cifhr_heads_workspace_size(const Heads &h, int n_img, int K);
 // dense (n_img * K, hh, pitch) map, every pixel written
 template <bool DET>

@@ -1493,16 +1493,36 @@ __global__ __launch_bounds__(256) void caf_bucketed_ragged_kernel(CafBArgs a, co
     caf_bucketed_body<false, true>(a, ext);
 }
 
-static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+// The seeds scratch of one batch (host only): the emission slots g_keys (n_img, 4, cap) at
+// offset 0 and g_f (n_img, cap), the segment counts f_counts (n_img, kMaxHeads * PP_MAX_KP),
+// and the sort's permutation g_perm (n_img, np_cap), np_cap = twice cap rounded up to a power
+// of two.  The fused CifHr kernels write through seed_sink's pointers and the sort reads
+// through launch_seeds's: both take them from here.
+struct SeedsScratch {
+    size_t off_f, off_counts, off_perm, total;
+    int64_t np_cap;
+};
+
+static SeedsScratch seeds_scratch(int n_img, int cap) {
+    int64_t np = 1;
+    while (np < cap) np <<= 1;
+    SeedsScratch l;
+    l.np_cap = 2 * np;
+    l.off_f = round_up((int64_t)n_img * 4 * cap * sizeof(float), 256);
+    l.off_counts = l.off_f + round_up((int64_t)n_img * cap * sizeof(int), 256);
+    l.off_perm = l.off_counts + round_up((int64_t)n_img * kMaxHeads * PP_MAX_KP * sizeof(int), 256);
+    l.total = l.off_perm + round_up((int64_t)n_img * l.np_cap * sizeof(int), 256);
+    return l;
+}
+
+size_t seeds_scratch_size(int n_img, int cap) { return seeds_scratch(n_img, cap).total; }
 
 SeedSink seed_sink(int n_img, int K, const pp_config *cfg, int cap, void *scratch) {
+    const SeedsScratch l = seeds_scratch(n_img, cap);
     SeedSink k{};
-    char *w = (char *)scratch;
-    k.g_keys = (float *)w;
-    w += round_up((int64_t)n_img * 4 * cap * sizeof(float), 256);
-    k.g_f = (int *)w;
-    w += round_up((int64_t)n_img * cap * sizeof(int), 256);
-    k.f_counts = (int *)w;
+    k.g_keys = (float *)scratch;
+    k.g_f = (int *)((char *)scratch + l.off_f);
+    k.f_counts = (int *)((char *)scratch + l.off_counts);
     k.cap = cap;
     k.K = K;
     k.th = cfg->seed_threshold;
@@ -1529,17 +1549,12 @@ int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_con
     a.seeds = seeds;
     a.cap = cap;
     a.counts = counts;
-    int np = 1;
-    while (np < cap) np <<= 1;
-    a.np_cap = 2 * np;
-    char *w = (char *)scratch;
-    a.g_keys = (float *)w;
-    w += round_up((int64_t)n_img * 4 * cap * sizeof(float), 256);
-    a.g_f = (int *)w;
-    w += round_up((int64_t)n_img * cap * sizeof(int), 256);
-    a.f_counts = (int *)w;
-    w += round_up((int64_t)n_img * kMaxHeads * PP_MAX_KP * sizeof(int), 256);
-    a.g_perm = (int *)w;
+    const SeedsScratch l = seeds_scratch(n_img, cap);
+    a.np_cap = (int)l.np_cap;
+    a.g_keys = (float *)scratch;
+    a.g_f = (int *)((char *)scratch + l.off_f);
+    a.f_counts = (int *)((char *)scratch + l.off_counts);
+    a.g_perm = (int *)((char *)scratch + l.off_perm);
     if (!emitted && ext)
         hipLaunchKernelGGL(seeds_emit_ragged_kernel, dim3((unsigned)((int64_t)n_img * h.n_cif * K)), dim3(256), 0, s, a, ext);
     else if (!emitted)
@@ -1568,15 +1583,6 @@ int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_con
     }
 #endif
     return check_launch("pp_seeds");
-}
-
-size_t seeds_scratch_size(int n_img, int cap) {
-    int64_t np = 1;
-    while (np < cap) np <<= 1;
-    return round_up((int64_t)n_img * 4 * cap * sizeof(float), 256) +
-           round_up((int64_t)n_img * cap * sizeof(int), 256) +
-           round_up((int64_t)n_img * kMaxHeads * PP_MAX_KP * sizeof(int), 256) +
-           round_up((int64_t)n_img * 2 * np * sizeof(int), 256);
 }
 
 int launch_caf_scored(const Heads &h, const HrMap &hr, int n_img, int K, int C,

@@ -44,6 +44,44 @@ def run(old, new):
     return bad, lines
 
 
+FAKE_BUILD = '''import os
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+CSRC = os.path.join(HERE, 'csrc')
+HIPCC = 'hipcc'
+CFLAGS = ['-O3', '-I', os.path.join(REPO, 'include')]
+FILE_FLAGS = {file_flags!r}
+VARIANTS = {variants!r}
+'''
+
+
+def test_each_tree_is_compiled_with_its_own_builds_flags(tmp_path):
+    """Code that left a.hip for b.hip: the old tree flags a.hip, the new one both, and each
+    tree's command lines carry its own build.py's per-file flags, variant defines and paths."""
+    trees = {}
+    for tree, file_flags, variants in (('old', {'a.hip': ['-fno-x']}, {'stamps': ['-DOLD_STAMPS']}),
+                                       ('new', {'a.hip': ['-fno-x'], 'b.hip': ['-fno-x']},
+                                        {'stamps': ['-DNEW_STAMPS']})):
+        pkg = tmp_path / tree / 'openpifpaf_amd'
+        (pkg / 'csrc').mkdir(parents=True)
+        (pkg / 'build.py').write_text(FAKE_BUILD.format(file_flags=file_flags, variants=variants))
+        trees[tree] = isa_diff.tree_build(str(tmp_path / tree))
+    old, new = trees['old'], trees['new']
+    assert old is not new and old.FILE_FLAGS != new.FILE_FLAGS
+    for name, old_has, new_has in (('a.hip', True, True), ('b.hip', False, True), ('c.hip', False, False)):
+        co = isa_diff.command(old, name, '', 'o.s')
+        cn = isa_diff.command(new, name, '', 'n.s')
+        assert ('-fno-x' in co, '-fno-x' in cn) == (old_has, new_has)
+        # each tree's own source and include directory
+        assert str(tmp_path / 'old' / 'openpifpaf_amd' / 'csrc' / name) in co
+        assert str(tmp_path / 'new' / 'openpifpaf_amd' / 'csrc' / name) in cn
+        assert str(tmp_path / 'old' / 'include') in co and str(tmp_path / 'new' / 'include') in cn
+        assert str(tmp_path / 'new') not in ' '.join(co) and str(tmp_path / 'old') not in ' '.join(cn)
+    so, sn = isa_diff.command(old, 'b.hip', 'stamps', 'o.s'), isa_diff.command(new, 'b.hip', 'stamps', 'n.s')
+    assert '-DOLD_STAMPS' in so and '-DNEW_STAMPS' not in so
+    assert '-DNEW_STAMPS' in sn and '-DOLD_STAMPS' not in sn and '-fno-x' in sn and '-fno-x' not in so
+
+
 def test_moved_and_renumbered_code_is_same():
     old = {'a.hip': kernel('k1', 0) + kernel('k2', 1) + FUNC.format(name='f', n=2, imm=1)}
     new = {'b.hip': kernel('k2', 0) + FUNC.format(name='f', n=1, imm=1),

@@ -1,43 +1,56 @@
 """Does a refactor change the generated gfx950 code?  Compares two source trees by symbol:
     python tools/isa_diff.py PARENT_TREE NEW_TREE [variant]
 Each tree is a repository root (a `git archive` of the parent commit, and the working tree).
-Every csrc/*.hip of each is compiled to device assembly with the flags of build.py (and the
-variant's defines, e.g. `stamps`); the assembly is split by function symbol, comments go,
-the numbers in local labels are replaced, and each symbol is compared ACROSS the files of a
-tree (code may have moved to another file).  hipcc emits a kernel's .amdhsa_kernel block
+Every csrc/*.hip of each is compiled to device assembly with the flags of that tree's own
+openpifpaf_amd/build.py (its per-file flags and its variant's defines, e.g. `stamps`: code
+that moved to another file is built as each tree's build would build it); the assembly is
+split by function symbol, comments go, the numbers in local labels are replaced, and each
+symbol is compared ACROSS the files of a tree (code may have moved to another file).  hipcc emits a kernel's .amdhsa_kernel block
 (registers, LDS, scratch) inside the function's .type ... .size range, so it is compared with
 the code, and it marks the symbol as a kernel.  Needs no GPU.  Exits 1 on any DIFF or on a
 kernel missing from NEW_TREE."""
 import concurrent.futures
+import importlib.util
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from openpifpaf_amd import build as b
-
 LABEL = re.compile(r'(\.L[A-Za-z_]+?)\d+')
+
+
+def tree_build(tree):
+    """The tree's own openpifpaf_amd/build.py as a module, loaded by path: each tree is
+    compiled with the flags its own build gives it (CFLAGS with its include directory,
+    FILE_FLAGS by file name, VARIANTS)."""
+    path = os.path.join(tree, 'openpifpaf_amd', 'build.py')
+    spec = importlib.util.spec_from_file_location('isa_diff_tree_build', path)  # not registered
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def command(b, name, variant, out):
+    """The hipcc line for the device assembly of csrc/`name` under the tree's build module b"""
+    return ([b.HIPCC] + b.CFLAGS + b.FILE_FLAGS.get(name, []) + b.VARIANTS.get(variant, []) +
+            ['--cuda-device-only', '-S', os.path.join(b.CSRC, name), '-o', out])
 
 
 def assembly(tree, variant, tmp):
     """{file name: device assembly text} of the tree's csrc/*.hip"""
-    csrc = os.path.join(tree, 'openpifpaf_amd', 'csrc')
-    flags = [os.path.join(tree, 'include') if f == os.path.join(b.REPO, 'include') else f
-             for f in b.CFLAGS]
+    b = tree_build(tree)
 
     def one(name):
         out = os.path.join(tmp, name[:-4] + '.s')
-        cmd = ([b.HIPCC] + flags + b.FILE_FLAGS.get(name, []) + b.VARIANTS.get(variant, []) +
-               ['--cuda-device-only', '-S', os.path.join(csrc, name), '-o', out])
+        cmd = command(b, name, variant, out)
         res = subprocess.run(cmd, capture_output=True, text=True, check=False)
         if res.returncode != 0:
             raise RuntimeError('hipcc failed: {}\n{}'.format(' '.join(cmd), res.stderr))
         with open(out) as f:
             return name, f.read()
 
-    names = sorted(f for f in os.listdir(csrc) if f.endswith('.hip'))
+    names = sorted(f for f in os.listdir(b.CSRC) if f.endswith('.hip'))
     with concurrent.futures.ThreadPoolExecutor(8) as ex:
         return dict(ex.map(one, names))
 
