@@ -1,6 +1,13 @@
-// decode.hip — host side of the decoder: the workspace layout, the stage sequence of a
-// decode (decode_heads) and the pp_decode_* entry points.  The kernels and their
-// launchers are in seed_loop.hip, seed_loop_ext.hip, complete.hip and nms.hip.
+// decode.hip — host side of the decoder.  The kernels and their launchers are in
+// seed_loop.hip, seed_loop_ext.hip, complete.hip and nms.hip.  In the order of the file:
+//   DecodeLayout / make_layout and the six size / offset exports: the workspace layout;
+//   SideStream / SideFork: the library's side stream and one fork / join of it;
+//   check_decode: every refusal of a decode, before anything touches HIP;
+//   DecodeRegions / decode_regions: the workspace regions as typed pointers;
+//   grow_args: the GrowArgs of stage 8 (the skeleton through by_source.hpp's BySource);
+//   stamps_begin / stamps_end: the diagnostic build's buffers and their dump;
+//   decode_heads: the stage sequence, behind all five pp_decode_* entry points.
+#include "by_source.hpp"
 #include "grow_args.hpp"
 
 #include <stdio.h>
@@ -8,9 +15,6 @@
 
 #include <mutex>
 
-// ---------------------------------------------------------------------------------------
-// host: workspace layout + pp_decode_batch
-// ---------------------------------------------------------------------------------------
 namespace pp {
 
 int launch_seeds(const Heads &h, const HrMap &hr, int n_img, int K, const pp_config *cfg,
@@ -213,11 +217,30 @@ static int seed_ext_per_image(int n_img) {
     return std::max(0, std::min(kExtWgMax, cus[dev] / n_img - 1));
 }
 
-// Force-complete workgroups per image.  The workgroups pull annotations from a per-image
-// counter, so any count gives the same result; 8 or 16 for sparse batches measured no
-// better than 64 (round 5).
-static int complete_ways(uint32_t) { return kCompleteWays; }
+// One fork of the side stream off the caller's stream s: the side stream's lock, held from
+// here to the end of the scope, and the fork events (the side stream waits for what s holds
+// now).  join() makes s wait for what the side stream holds then.
+struct SideFork {
+    const SideStream *side;
+    hipStream_t s;
+    std::lock_guard<std::mutex> lock;
+    bool forked;
 
+    SideFork(const SideStream *ss, hipStream_t caller)
+        : side(ss), s(caller), lock(ss->mu),
+          forked(hipEventRecord(ss->fork, caller) == hipSuccess &&
+                 hipStreamWaitEvent(ss->stream, ss->fork, 0) == hipSuccess) {}
+    bool join() const {
+        return hipEventRecord(side->join, side->stream) == hipSuccess &&
+               hipStreamWaitEvent(s, side->join, 0) == hipSuccess;
+    }
+};
+
+// the stage bits that include/pifpaf_amd.h gives as numbers (pp_decode_stages)
+constexpr uint32_t kStageCifHr = 1u, kStageSeeds = 2u, kStageCafScored = 4u;
+constexpr uint32_t kStageGrow = 8u;  // seed loop, force-complete and NMS
+constexpr uint32_t kStageSeedsAndCaf = kStageSeeds | kStageCafScored;
+constexpr uint32_t kStageAll = kStageCifHr | kStageSeedsAndCaf | kStageGrow;
 
 // optional inputs of pp_decode_initial
 struct DecodeInit {
@@ -229,11 +252,13 @@ struct DecodeInit {
     const int32_t *extents = nullptr;
 };
 
-static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
-                        const int32_t *skeleton, const pp_config *cfg, float *d_cifhr,
-                        pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
-                        int32_t *d_status, void *d_workspace, size_t workspace_bytes,
-                        uint32_t stages, void *stream, const DecodeInit &init = DecodeInit{}) {
+// Every refusal of a decode, in this order and before anything touches HIP; the messages
+// name pp_decode_batch whichever entry point was called.  An empty batch is PP_OK with *d
+// left alone: the caller returns on `rc || n_img == 0`.
+static int check_decode(const Heads &h, int32_t n_img, int32_t K, int32_t C,
+                        const int32_t *skeleton, const pp_config *cfg, const pp_ann *d_anns,
+                        int32_t ann_capacity, const int32_t *d_counts, const int32_t *d_status,
+                        const void *d_workspace, size_t workspace_bytes, DecodeLayout *d) {
     if (!skeleton || !cfg || !d_anns || !d_counts || !d_status || !d_workspace)
         return fail(PP_EINVAL, "pp_decode_batch: NULL argument");
     for (int m = 0; m < h.n_cif; m++)
@@ -252,57 +277,225 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
     if ((int64_t)K * h.cif_cells() > INT32_MAX || h.caf_cells() > INT32_MAX)
         return fail(PP_ESHAPE, "pp_decode_batch: fields too large");
     if (n_img == 0) return PP_OK;
-    const DecodeLayout d = make_layout(n_img, K, C, h, cfg, ann_capacity);
-    if (workspace_bytes < d.total) return fail(PP_ENOMEM, "pp_decode_batch: workspace too small");
-    if ((int64_t)d.hh >= kMaxHrSide || (int64_t)d.ww >= kMaxHrSide)
+    *d = make_layout(n_img, K, C, h, cfg, ann_capacity);
+    if (workspace_bytes < d->total) return fail(PP_ENOMEM, "pp_decode_batch: workspace too small");
+    if ((int64_t)d->hh >= kMaxHrSide || (int64_t)d->ww >= kMaxHrSide)
         return fail(PP_ESHAPE, "pp_decode_batch: field too large (CifHr map of 32768 px or "
                                "more per side)");
+    return PP_OK;
+}
+
+// The workspace regions of a decode as typed pointers.
+struct DecodeRegions {
+    // the caller's d_cifhr gets the dense map; otherwise the decoder keeps the block-sparse
+    // scratch map (hr_masks, and hr_aux with more than one CifHr group), written only where
+    // splat boxes land
+    float *hr_base, *hr_aux;
+    uint64_t *hr_masks;
+    HrMap hr;
+    char *cifhr_ws, *seed_ws;
+    pp_seed *seeds;
+    int *seed_counts;
+    float *cols[2];
+    int *offs[2];
+    // what only stage 8 reads, in the GrowArgs it reads them through: the regions and the
+    // five above that its kernels read too, every other field zero (grow_args sets those)
+    GrowArgs grow;
+};
+
+static DecodeRegions decode_regions(const DecodeLayout &d, void *d_workspace, float *d_cifhr) {
     char *ws = (char *)d_workspace;
+    DecodeRegions p{};
+    p.hr_base = d_cifhr ? d_cifhr : (float *)(ws + d.off_cifhr);
+    p.hr_aux = (float *)(ws + d.off_hr_aux);
+    p.hr_masks = d_cifhr ? nullptr : (uint64_t *)(ws + d.off_hr_masks);
+    p.hr = dense_hr(p.hr_base, d.hh, d.ww);
+    p.hr.masks = p.hr_masks;
+    p.cifhr_ws = ws + d.off_cifhr_ws;
+    p.seed_ws = ws + d.off_seed_ws;
+    p.seeds = (pp_seed *)(ws + d.off_seeds);
+    p.seed_counts = (int *)(ws + d.off_seed_counts);
+    GrowArgs &g = p.grow;
+    g.hr = p.hr;
+    g.seeds = p.seeds;
+    g.seed_counts = p.seed_counts;
+    for (int t = 0; t < 2; t++) {
+        g.cols[t] = p.cols[t] = (float *)(ws + d.off_cols[t]);
+        g.offs[t] = p.offs[t] = (int *)(ws + d.off_offs[t]);
+    }
+    g.n_work = (int *)(ws + d.off_n_work);
+    g.need_complete = (int *)(ws + d.off_need);
+    g.complete_next = (int *)(ws + d.off_wq);
+    g.occ = (uint8_t *)(ws + d.off_occ);
+    g.log = (OccLog *)(ws + d.off_log);
+    g.work = (pp_ann *)(ws + d.off_work);
+    g.spec = (pp_ann *)(ws + d.off_spec);
+    g.xext = (SeedExt *)(ws + d.off_xext);
+    g.xrec = (pp_ann *)(ws + d.off_xrec);
+    g.nms_score = (double *)(ws + d.off_nms_score);
+    g.nms_idx = (int *)(ws + d.off_nms_idx);
+    g.nms_f = (float *)(ws + d.off_nms_f);
+    g.nms_box = (int2 *)(ws + d.off_nms_box);
+    return p;
+}
+
+// GrowArgs of stage 8: the workspace regions, then the decode's shapes and options, the
+// skeleton as directed-edge slots, the optional initial annotations and the outputs.
+static GrowArgs grow_args(const Heads &h, int32_t n_img, int32_t K, int32_t C,
+                          const int32_t *skeleton, const pp_config *cfg, const DecodeLayout &d,
+                          const DecodeRegions &p, const DecodeInit &init, pp_ann *d_anns,
+                          int32_t ann_capacity, int32_t *d_counts, int32_t *d_status) {
+    GrowArgs g = p.grow;
+    g.seed_cap = d.seed_cap;
+    g.bw = d.bw;
+    g.bh = d.bh;
+    g.nb = d.nb;
+    g.inv_e = d.inv_e;
+    g.K = K;
+    g.C = C;
+    g.hh = d.hh;
+    g.ww = d.ww;
+    g.col_cap = d.hw;
+    g.cfg = *cfg;
+    g.nms_it = (double)cfg->nms_instance_threshold;
+    g.heads = h;
+    g.cif_floor = cfg->cif_floor;
+    g.one_minus_floor = (float)(1.0 - (double)cfg->cif_floor);  // (1.0 - self.cif_floor)
+    g.th_b = cfg->complete_caf_threshold;
+    for (int ci = 0; ci < C; ci++) {
+        g.caf_j1[ci] = (uint8_t)(skeleton[2 * ci] - 1);
+        g.caf_j2[ci] = (uint8_t)(skeleton[2 * ci + 1] - 1);
+    }
+    // by_source flattened into directed-edge slots per start joint
+    const BySource bs(skeleton, C);
+    int nd = 0;
+    for (int j = 0; j < K; j++) {
+        g.j_off[j] = (uint8_t)nd;
+        for (int e = 0; e < bs.n[j]; e++, nd++) {
+            g.d_j[nd] = (uint8_t)j;
+            g.d_k[nd] = (uint8_t)bs.end[j][e];
+            g.d_caf[nd] = (uint8_t)bs.caf[j][e];
+            g.d_fwd[nd] = (uint8_t)bs.fwd[j][e];
+        }
+    }
+    g.j_off[K] = (uint8_t)nd;
+    g.nd = nd;
+    g.has_cs = cfg->confidence_scales != nullptr;
+    for (int e = 0; e < kSlots; e++)
+        g.slot_cs[e] = (g.has_cs && e < nd) ? cfg->confidence_scales[g.d_caf[e]] : 1.0f;
+    g.occ_cap = d.occ_cap;
+    g.log_cap = d.log_cap;
+    g.spec_far = kSpecFar;
+    g.n_ext = seed_ext_per_image(n_img);
+    g.ann_np = d.ann_np;
+    g.ann_cap = ann_capacity;
+    g.init = init.anns;
+    g.init_counts = init.counts;
+    g.init_cap = init.cap;
+    g.out_idx = init.out_index;
+    g.out = d_anns;
+    g.counts = d_counts;
+    g.status = d_status;
+    return g;
+}
+
+// The diagnostic build's cycle sums (grow_args.hpp): stamps_begin allocates and zeroes them
+// before stage 8's first launch, stamps_end waits for the stream after its last, appends the
+// kernels' sums to $PP_STAMPS_OUT and prints grow_connection's.
+#ifdef PP_STAMPS
+static void stamps_begin(GrowArgs &g, int n_img, hipStream_t s) {
+    hipMalloc((void **)&g.stamps, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t));
+    hipMemsetAsync(g.stamps, 0, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t), s);
+    hipMalloc((void **)&g.gc_stamps, (size_t)n_img * 4 * sizeof(uint64_t));
+    hipMemsetAsync(g.gc_stamps, 0, (size_t)n_img * 4 * sizeof(uint64_t), s);
+}
+
+static void stamps_end(const GrowArgs &g, int n_img, hipStream_t s) {
+    hipStreamSynchronize(s);
+    const size_t nst = (size_t)n_img * 3 * kStampSlots;
+    uint64_t *hs = (uint64_t *)malloc(nst * sizeof(uint64_t));
+    hipMemcpy(hs, g.stamps, nst * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    const char *path = getenv("PP_STAMPS_OUT");
+    FILE *fo = fopen(path ? path : "pp_stamps.bin", "ab");
+    if (fo) {
+        fwrite(hs, sizeof(uint64_t), nst, fo);
+        fclose(fo);
+    }
+    free(hs);
+    hipFree(g.stamps);
+    uint64_t *hg = (uint64_t *)malloc((size_t)n_img * 4 * sizeof(uint64_t));
+    hipMemcpy(hg, g.gc_stamps, (size_t)n_img * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    double a0 = 0, a1 = 0, a2 = 0;
+    for (int i = 0; i < n_img; i++) {
+        a0 += hg[4 * i];
+        a1 += hg[4 * i + 1];
+        a2 += hg[4 * i + 2];
+    }
+    fprintf(stderr, "grow_connection sections per image: offsets+scan-setup %.0f  columns %.0f  merge %.0f\n",
+            a0 / n_img, a1 / n_img, a2 / n_img);
+    free(hg);
+    hipFree(g.gc_stamps);
+}
+#else
+static void stamps_begin(GrowArgs &, int, hipStream_t) {}
+static void stamps_end(const GrowArgs &, int, hipStream_t) {}
+#endif
+
+// The stage sequence of a decode, behind all five entry points.
+static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
+                        const int32_t *skeleton, const pp_config *cfg, float *d_cifhr,
+                        pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
+                        int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                        uint32_t stages, void *stream, const DecodeInit &init = DecodeInit{}) {
+    DecodeLayout d;
+    int rc = check_decode(h, n_img, K, C, skeleton, cfg, d_anns, ann_capacity, d_counts, d_status,
+                          d_workspace, workspace_bytes, &d);
+    if (rc || n_img == 0) return rc;
+    const DecodeRegions p = decode_regions(d, d_workspace, d_cifhr);
     hipStream_t s = (hipStream_t)stream;
     const int32_t *ext = init.extents;
-    // the caller's d_cifhr gets the dense map; otherwise the decoder keeps the block-sparse
-    // scratch map, written only where splat boxes land
-    float *hr_base = d_cifhr ? d_cifhr : (float *)(ws + d.off_cifhr);
-    uint64_t *hr_masks = d_cifhr ? nullptr : (uint64_t *)(ws + d.off_hr_masks);
-    HrMap hr = dense_hr(hr_base, d.hh, d.ww);
-    hr.masks = hr_masks;
-    pp_seed *seeds = (pp_seed *)(ws + d.off_seeds);
-    int *seed_counts = (int *)(ws + d.off_seed_counts);
-    float *cols[2] = {(float *)(ws + d.off_cols[0]), (float *)(ws + d.off_cols[1])};
-    int *offs[2] = {(int *)(ws + d.off_offs[0]), (int *)(ws + d.off_offs[1])};
-    int rc = PP_OK;
+    // CafScored on stream `on`: set A at caf_threshold; set B, the force-complete set at
+    // complete_caf_threshold (cell indices only), for the images `gate` marks (NULL: all)
+    auto caf_a = [&](hipStream_t on) {
+        return launch_caf_bucketed(h, p.hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold,
+                                   p.cols[0], p.offs[0], nullptr, false, on, ext);
+    };
+    auto caf_b = [&](hipStream_t on, const int *gate) {
+        return launch_caf_bucketed(h, p.hr, n_img, K, C, skeleton, cfg,
+                                   cfg->complete_caf_threshold, p.cols[1], p.offs[1], gate, true,
+                                   on, ext);
+    };
     // PP_STAGE_COMPLETE_SETS_EARLY with stage 1 (and without 8): the force-complete sets read
     // only the CAF fields, so they start on the side stream before the CifHr map, and a later
     // call's side-stream join (stages 2 | 4) covers them
-    const bool b_first = (stages & PP_STAGE_COMPLETE_SETS_EARLY) && (stages & 1u) &&
-                         !(stages & 8u) && cfg->force_complete;
-    if (b_first) {
+    const bool sets_early = (stages & PP_STAGE_COMPLETE_SETS_EARLY) && cfg->force_complete;
+    if (sets_early && (stages & kStageCifHr) && !(stages & kStageGrow)) {
         const SideStream *side = side_stream();
         if (!side) return fail(PP_EHIP, "pp_decode_stages: no side stream for stage 16");
-        std::lock_guard<std::mutex> lock(side->mu);
-        if (hipEventRecord(side->fork, s) != hipSuccess ||
-            hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
-        rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                 cols[1], offs[1], nullptr, true, side->stream, ext);
+        const SideFork fork(side, s);
+        if (!fork.forked) return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
+        rc = caf_b(side->stream, nullptr);
         if (rc) {
-            (void)hipEventRecord(side->join, side->stream);
-            (void)hipStreamWaitEvent(s, side->join, 0);
+            (void)fork.join();
             return rc;
         }
     }
     // the block-sparse map's kernel emits the seeds too when it can (stage 1 then writes
     // what seeds_emit_kernel would; stage 2 sorts them): the same test in both stages
     const bool fused_seeds = !d_cifhr && cifhr_fuses_seeds(h, n_img, K, cfg);
-    if (stages & 1u) {
+    auto seeds = [&]() {
+        return launch_seeds(h, p.hr, n_img, K, cfg, p.seeds, d.seed_cap, p.seed_counts, p.seed_ws,
+                            s, fused_seeds, ext);
+    };
+    if (stages & kStageCifHr) {
         if (d_cifhr) {
-            rc = cifhr_heads_launch<false>(h, n_img, K, cfg, d_cifhr, ws + d.off_cifhr_ws,
+            rc = cifhr_heads_launch<false>(h, n_img, K, cfg, d_cifhr, p.cifhr_ws,
                                            d.cifhr_ws_bytes, s, "pp_decode_batch(cifhr)");
         } else {
-            const SeedSink sink = seed_sink(n_img, K, cfg, d.seed_cap, ws + d.off_seed_ws);
-            rc = cifhr_sparse_launch(h, n_img, K, cfg, hr_base, (float *)(ws + d.off_hr_aux),
-                                     hr_masks, ws + d.off_cifhr_ws, d.cifhr_ws_bytes, s,
-                                     "pp_decode_batch(cifhr)", fused_seeds ? &sink : nullptr, ext);
+            const SeedSink sink = seed_sink(n_img, K, cfg, d.seed_cap, p.seed_ws);
+            rc = cifhr_sparse_launch(h, n_img, K, cfg, p.hr_base, p.hr_aux, p.hr_masks,
+                                     p.cifhr_ws, d.cifhr_ws_bytes, s, "pp_decode_batch(cifhr)",
+                                     fused_seeds ? &sink : nullptr, ext);
         }
         if (rc) return rc;
     }
@@ -310,143 +503,33 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
     // requested, CafScored runs on a side stream beside the seeds (fork / join events)
     // PP_STAGE_COMPLETE_SETS_EARLY: the force-complete sets (every field and direction) with
     // CafScored instead of gated after the seed loop
-    const bool early_b = (stages & PP_STAGE_COMPLETE_SETS_EARLY) && (stages & 4u) &&
-                         !(stages & 1u) && cfg->force_complete;
-    const SideStream *side = (stages & 6u) == 6u ? side_stream() : nullptr;
+    const bool early_b = sets_early && (stages & kStageCafScored) && !(stages & kStageCifHr);
+    const SideStream *side =
+        (stages & kStageSeedsAndCaf) == kStageSeedsAndCaf ? side_stream() : nullptr;
     if (side) {
-        std::lock_guard<std::mutex> lock(side->mu);
-        if (hipEventRecord(side->fork, s) != hipSuccess ||
-            hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
-        rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold, cols[0],
-                                 offs[0], nullptr, false, side->stream, ext);
-        if (!rc && early_b)
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
-                                     cfg->complete_caf_threshold, cols[1], offs[1], nullptr, true,
-                                     side->stream, ext);
-        if (!rc)
-            rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds, ext);
+        const SideFork fork(side, s);
+        if (!fork.forked) return fail(PP_EHIP, "pp_decode_batch: side-stream fork failed");
+        rc = caf_a(side->stream);
+        if (!rc && early_b) rc = caf_b(side->stream, nullptr);
+        if (!rc) rc = seeds();
         // join even after a failed launch, so the caller's stream never runs ahead
-        if (hipEventRecord(side->join, side->stream) != hipSuccess ||
-            hipStreamWaitEvent(s, side->join, 0) != hipSuccess)
-            return fail(PP_EHIP, "pp_decode_batch: side-stream join failed");
+        if (!fork.join()) return fail(PP_EHIP, "pp_decode_batch: side-stream join failed");
         if (rc) return rc;
     } else {
-        if (stages & 2u) {
-            rc = launch_seeds(h, hr, n_img, K, cfg, seeds, d.seed_cap, seed_counts,
-                              ws + d.off_seed_ws, s, fused_seeds, ext);
+        if (stages & kStageSeeds) {
+            rc = seeds();
             if (rc) return rc;
         }
-        if (stages & 4u) {  // CafScored at caf_threshold; the force-complete set is lazy
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->caf_threshold,
-                                     cols[0], offs[0], nullptr, false, s, ext);
-            if (!rc && early_b)
-                rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg,
-                                         cfg->complete_caf_threshold, cols[1], offs[1], nullptr,
-                                         true, s, ext);
+        if (stages & kStageCafScored) {  // the force-complete set is lazy unless early_b
+            rc = caf_a(s);
+            if (!rc && early_b) rc = caf_b(s, nullptr);
             if (rc) return rc;
         }
     }
-    if (stages & 8u) {
-        GrowArgs g{};
-        g.seeds = seeds;
-        g.seed_counts = seed_counts;
-        g.seed_cap = d.seed_cap;
-        g.cols[0] = cols[0];
-        g.cols[1] = cols[1];
-        g.offs[0] = offs[0];
-        g.offs[1] = offs[1];
-        g.bw = d.bw;
-        g.bh = d.bh;
-        g.nb = d.nb;
-        g.inv_e = d.inv_e;
-        g.K = K;
-        g.C = C;
-        g.hh = d.hh;
-        g.ww = d.ww;
-        g.col_cap = d.hw;
-        g.cfg = *cfg;
-        g.nms_it = (double)cfg->nms_instance_threshold;
-        g.heads = h;
-        g.hr = hr;
-        g.cif_floor = cfg->cif_floor;
-        g.one_minus_floor = (float)(1.0 - (double)cfg->cif_floor);  // (1.0 - self.cif_floor)
-        g.th_b = cfg->complete_caf_threshold;
-        for (int ci = 0; ci < C; ci++) {
-            g.caf_j1[ci] = (uint8_t)(skeleton[2 * ci] - 1);
-            g.caf_j2[ci] = (uint8_t)(skeleton[2 * ci + 1] - 1);
-        }
-        // by_source (cifcaf.py:62-65): dict insertion order, later duplicate keys
-        // overwrite the value in place; flattened into directed-edge slots per start joint
-        {
-            int nbs[kKP] = {0};
-            int bk[kKP][kKP], bc[kKP][kKP], bf[kKP][kKP];
-            for (int ci = 0; ci < C; ci++) {
-                const int j1 = skeleton[2 * ci] - 1, j2 = skeleton[2 * ci + 1] - 1;
-                const int ins[2][3] = {{j1, j2, 1}, {j2, j1, 0}};
-                for (int t = 0; t < 2; t++) {
-                    const int st = ins[t][0];
-                    int pos = -1;
-                    for (int e = 0; e < nbs[st]; e++)
-                        if (bk[st][e] == ins[t][1]) pos = e;
-                    if (pos < 0) pos = nbs[st]++;
-                    bk[st][pos] = ins[t][1];
-                    bc[st][pos] = ci;
-                    bf[st][pos] = ins[t][2];
-                }
-            }
-            int d = 0;
-            for (int j = 0; j < K; j++) {
-                g.j_off[j] = (uint8_t)d;
-                for (int e = 0; e < nbs[j]; e++, d++) {
-                    g.d_j[d] = (uint8_t)j;
-                    g.d_k[d] = (uint8_t)bk[j][e];
-                    g.d_caf[d] = (uint8_t)bc[j][e];
-                    g.d_fwd[d] = (uint8_t)bf[j][e];
-                }
-            }
-            g.j_off[K] = (uint8_t)d;
-            g.nd = d;
-            g.has_cs = cfg->confidence_scales != nullptr;
-            for (int e = 0; e < kSlots; e++)
-                g.slot_cs[e] = (g.has_cs && e < d) ? cfg->confidence_scales[g.d_caf[e]] : 1.0f;
-        }
-        g.occ = (uint8_t *)(ws + d.off_occ);
-        g.occ_cap = d.occ_cap;
-        g.log = (OccLog *)(ws + d.off_log);
-        g.log_cap = d.log_cap;
-        g.work = (pp_ann *)(ws + d.off_work);
-        g.spec = (pp_ann *)(ws + d.off_spec);
-        g.spec_far = kSpecFar;
-        g.n_ext = seed_ext_per_image(n_img);
-        g.xext = (SeedExt *)(ws + d.off_xext);
-        g.xrec = (pp_ann *)(ws + d.off_xrec);
-        g.nms_score = (double *)(ws + d.off_nms_score);
-        g.nms_idx = (int *)(ws + d.off_nms_idx);
-        g.nms_f = (float *)(ws + d.off_nms_f);
-        g.nms_box = (int2 *)(ws + d.off_nms_box);
-        g.ann_np = d.ann_np;
-        g.ann_cap = ann_capacity;
-        g.stamps = nullptr;
-#ifdef PP_STAMPS
-        hipMalloc((void **)&g.stamps, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t));
-        hipMemsetAsync(g.stamps, 0, (size_t)n_img * 3 * kStampSlots * sizeof(uint64_t), s);
-        uint64_t *gcs = nullptr;
-        hipMalloc((void **)&gcs, (size_t)n_img * 4 * sizeof(uint64_t));
-        hipMemsetAsync(gcs, 0, (size_t)n_img * 4 * sizeof(uint64_t), s);
-        g.gc_stamps = gcs;
-#endif
-        g.n_work = (int *)(ws + d.off_n_work);
-        g.need_complete = (int *)(ws + d.off_need);
-        g.complete_next = (int *)(ws + d.off_wq);
-        g.init = init.anns;
-        g.init_counts = init.counts;
-        g.init_cap = init.cap;
-        g.out_idx = init.out_index;
-        g.out = d_anns;
-        g.counts = d_counts;
-        g.status = d_status;
+    if (stages & kStageGrow) {
+        GrowArgs g = grow_args(h, n_img, K, C, skeleton, cfg, d, p, init, d_anns, ann_capacity,
+                               d_counts, d_status);
+        stamps_begin(g, n_img, s);
         // PP_STAGE_SEED_LOOP_ONLY / PP_STAGE_AFTER_SEED_LOOP split stage 8 in two calls
         const bool run_rest = !(stages & PP_STAGE_SEED_LOOP_ONLY);
         if (!(stages & PP_STAGE_AFTER_SEED_LOOP)) {
@@ -459,43 +542,20 @@ static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
         const bool run_nms = run_rest && !(stages & PP_STAGE_COMPLETE_ONLY);
         if (run_complete && cfg->force_complete && !(stages & PP_STAGE_COMPLETE_SETS_EARLY)) {
             // complete_annotations' CafScored(score_th=0.0001) only where phase 1 left work
-            rc = launch_caf_bucketed(h, hr, n_img, K, C, skeleton, cfg, cfg->complete_caf_threshold,
-                                     cols[1], offs[1], g.need_complete, true, s, ext);
+            rc = caf_b(s, g.need_complete);
             if (rc) return rc;
         }
         if (run_complete && cfg->force_complete) {
-            rc = launch_complete(g, n_img, complete_ways(stages), s, ext);
+            // kCompleteWays workgroups per image.  They pull annotations from a per-image
+            // counter, so any count gives the same result; 8 or 16 for sparse batches measured
+            // no better than 64 (round 5).
+            rc = launch_complete(g, n_img, kCompleteWays, s, ext);
             if (rc) return rc;
         }
         if (run_nms)
             rc = launch_nms(g, n_img, (stages & PP_STAGE_NMS_WIDE) && g.n_ext == 0,
                             (stages & PP_STAGE_NMS_BITMAP) != 0, s);
-#ifdef PP_STAMPS
-        hipStreamSynchronize(s);
-        const size_t nst = (size_t)n_img * 3 * kStampSlots;
-        uint64_t *h = (uint64_t *)malloc(nst * sizeof(uint64_t));
-        hipMemcpy(h, g.stamps, nst * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        const char *path = getenv("PP_STAMPS_OUT");
-        FILE *fo = fopen(path ? path : "pp_stamps.bin", "ab");
-        if (fo) {
-            fwrite(h, sizeof(uint64_t), nst, fo);
-            fclose(fo);
-        }
-        free(h);
-        hipFree(g.stamps);
-        uint64_t *hg = (uint64_t *)malloc((size_t)n_img * 4 * sizeof(uint64_t));
-        hipMemcpy(hg, gcs, (size_t)n_img * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int i = 0; i < n_img; i++) {
-            a0 += hg[4 * i];
-            a1 += hg[4 * i + 1];
-            a2 += hg[4 * i + 2];
-        }
-        fprintf(stderr, "grow_connection sections per image: offsets+scan-setup %.0f  columns %.0f  merge %.0f\n",
-                a0 / n_img, a1 / n_img, a2 / n_img);
-        free(hg);
-        hipFree(gcs);
-#endif
+        stamps_end(g, n_img, s);
     }
     return rc;
 }
@@ -582,8 +642,8 @@ int pp_decode_batch(const float *d_cif, const float *d_caf, int32_t n_img, int32
                     float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
                     int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream) {
     return pp_decode_stages(d_cif, d_caf, n_img, K, C, H, W, skeleton, cfg, d_cifhr, d_anns,
-                            ann_capacity, d_counts, d_status, d_workspace, workspace_bytes, 15u,
-                            stream);
+                            ann_capacity, d_counts, d_status, d_workspace, workspace_bytes,
+                            kStageAll, stream);
 }
 
 }  // extern "C"

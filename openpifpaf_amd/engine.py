@@ -275,6 +275,19 @@ class DecodeEngine:
             self._bufs = DecodeBuffers(key, n, k, c, h, w, cfg, cap, _device.require(), heads)
         return self._bufs
 
+    def _prepare(self, skeleton, n, k, c, h, w, cfg, cap, stages, heads=None):
+        """What every launch starts with: the skeleton as an array of c pairs, the annotation
+        capacity, the buffers of this shape and, for a call that starts stage 8, their next
+        slot.  Returns (skel, cap, buffers)."""
+        skel = skeleton_array(skeleton)
+        if len(skel) != c:
+            raise ValueError('skeleton has {} edges but caf has {} fields'.format(len(skel), c))
+        cap = cap or default_ann_capacity(h, w)
+        b = self.buffers(n, k, c, h, w, cfg, cap, heads)
+        if stages & STAGE_GROW and not stages & STAGE_AFTER_SEED_LOOP:
+            b.next_slot()
+        return skel, cap, b
+
     def launch(self, cif, caf, skeleton, cfg, cap=None, keep_cifhr=False, stages=STAGE_ALL,
                initial=None):
         """Enqueue the decode on the current stream; returns the DecodeBuffers.  `initial`
@@ -285,13 +298,7 @@ class DecodeEngine:
         c = caf.shape[1]
         if caf.shape[0] != n or caf.shape[3:] != cif.shape[3:]:
             raise ValueError('cif and caf batch / spatial shapes differ')
-        skel = skeleton_array(skeleton)
-        if len(skel) != c:
-            raise ValueError('skeleton has {} edges but caf has {} fields'.format(len(skel), c))
-        cap = cap or default_ann_capacity(h, w)
-        b = self.buffers(n, k, c, h, w, cfg, cap)
-        if stages & STAGE_GROW and not stages & STAGE_AFTER_SEED_LOOP:
-            b.next_slot()
+        skel, cap, b = self._prepare(skeleton, n, k, c, h, w, cfg, cap, stages)
         hr = b.cifhr_buffer() if keep_cifhr else None
         if initial is not None:
             arr = scale_list([(cif.data_ptr(), h, w)], [(caf.data_ptr(), h, w)], [cfg.stride],
@@ -328,15 +335,8 @@ class DecodeEngine:
     def launch_ragged(self, ragged, skeleton, cfg, cap=None, stages=STAGE_ALL):
         """pp_decode_ragged over a RaggedFields, with launch's buffers at the container's
         shape; returns the DecodeBuffers."""
-        skel = skeleton_array(skeleton)
-        if len(skel) != ragged.c:
-            raise ValueError('skeleton has {} edges but caf has {} fields'.format(len(skel),
-                                                                                  ragged.c))
         n, k, c, h, w = ragged.n, ragged.k, ragged.c, ragged.h, ragged.w
-        cap = cap or default_ann_capacity(h, w)
-        b = self.buffers(n, k, c, h, w, cfg, cap)
-        if stages & STAGE_GROW and not stages & STAGE_AFTER_SEED_LOOP:
-            b.next_slot()
+        skel, cap, b = self._prepare(skeleton, n, k, c, h, w, cfg, cap, stages)
         call('pp_decode_ragged', _device.ptr(ragged.cif), _device.ptr(ragged.caf), n, k, c, h, w,
              _device.ptr(ragged.extents), ragged.extents_host.ctypes.data_as(ctypes.c_void_p),
              skel.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cfg), ctypes.c_void_p(0),
@@ -349,14 +349,8 @@ class DecodeEngine:
                      initial=None):
         """pp_decode_multi over a HeadSet (pp_decode_initial with `initial`); returns the
         DecodeBuffers."""
-        skel = skeleton_array(skeleton)
-        if len(skel) != heads.c:
-            raise ValueError('skeleton has {} edges but caf has {} fields'.format(len(skel),
-                                                                                  heads.c))
-        cap = cap or default_ann_capacity(heads.h, heads.w)
-        b = self.buffers(heads.n, heads.k, heads.c, heads.h, heads.w, cfg, cap, heads)
-        if stages & STAGE_GROW and not stages & STAGE_AFTER_SEED_LOOP:
-            b.next_slot()
+        skel, cap, b = self._prepare(skeleton, heads.n, heads.k, heads.c, heads.h, heads.w, cfg,
+                                     cap, stages, heads)
         hr = b.cifhr_buffer() if keep_cifhr else None
         if initial is not None:
             self._launch_initial(b, heads.arr, heads.pairs, heads.n, heads.k, heads.c, skel, cfg,

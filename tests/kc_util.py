@@ -56,6 +56,15 @@ NAMES = tuple(CASES)
 CONNECTED = ('pair2', 'loop3', 'chain5', 'k8c7', 'k20c33', 'k24star', 'k24c64')
 VARIANT_CASES = ('k24c64', 'chain5')  # get 'max' and 'greedy' fixtures too
 
+# Skeletons that name an unordered pair more than once, so that by_source overwrites an entry
+# in place (cifcaf.py:62-65: the later CAF index and direction at the earlier position).
+# Outside NAMES: check_skeleton refuses them and they have no reference fixture; the oracle
+# is their reference.
+REPEATED = {
+    'rep3': (3, [(1, 2), (2, 3), (2, 1), (2, 3)]),
+    'rep4': (4, [(1, 2), (2, 3), (3, 4), (2, 1), (1, 2), (4, 3)]),
+}
+
 UNIFORM_SIZES = ((12, 15), (20, 23), (31, 34))
 PLANTED_SIZE = (33, 40)
 PLANTED_OBJECTS = 4

@@ -214,6 +214,181 @@ WORKSPACE_MULTI = [
     (8292642816, 7990205440, 8215257088), (8634183680, 7990205440, 8250351616)]
 
 
+def _decode_refusal_calls():
+    """[(label, entry point, arguments)]: bad calls to the five decode entry points.  Device
+    pointers are a dummy non-NULL value and workspace_bytes is 16 throughout, so that a call
+    whose own check were lost would still stop at `workspace too small`, before any HIP call."""
+    from openpifpaf_amd import constants
+    from openpifpaf_amd._abi import make_config, scale_list, skeleton_array
+    p = ctypes.c_void_p(16)
+    coco = skeleton_array(constants.COCO_PERSON_SKELETON)
+    keep = []  # what the argument lists point to
+
+    def ptr(arr):
+        keep.append(arr)
+        return arr.ctypes.data_as(ctypes.c_void_p)
+
+    def cfg(**kw):
+        raw = {key: kw.pop(key) for key in ('connection_method', 'occupancy_reduction')
+               if key in kw}
+        c = make_config(**kw)
+        for key, v in raw.items():
+            setattr(c, key, v)
+        keep.append(c)
+        return ctypes.byref(c)
+
+    def stages(cif=p, caf=p, n=1, k=17, c=19, h=8, w=8, skel=coco, config=None, cap=8, ws=p,
+               size=16):
+        return [cif, caf, n, k, c, h, w, None if skel is None else ptr(skel), config or cfg(),
+                None, p, cap, p, p, ws, ctypes.c_size_t(size), ctypes.c_uint32(15), None]
+
+    def batch(**kw):
+        a = stages(**kw)
+        return a[:16] + a[17:]
+
+    def ragged(extents=((8, 8),), d_extents=p, hr=None, **kw):
+        a = stages(**kw)
+        return (a[:7] + [d_extents, ptr(np.asarray(extents, np.int32))] + a[7:9] + [hr] +
+                a[10:])
+
+    one = scale_list([(16, 8, 8)], [(16, 8, 8)], [8], [8])
+    odd = scale_list([(16, 8, 8)] * 3, [(16, 8, 8)], [8] * 3, [8])
+    no_cif = scale_list([(0, 8, 8)], [(16, 8, 8)], [8], [8])
+    keep.extend([one, odd, no_cif])
+
+    def multi(arr=one, pairs=0, n=1, k=17, c=19, skel=coco, config=None, cap=8, size=16):
+        return [arr, len(arr), pairs, n, k, c, ptr(skel), config or cfg(), None, p, cap, p, p, p,
+                ctypes.c_size_t(size), ctypes.c_uint32(15), None]
+
+    def initial(init=p, init_counts=p, init_cap=4, **kw):
+        a = multi(**kw)
+        return a[:13] + [init, init_counts, init_cap, None] + a[13:]
+
+    wide = np.tile(np.array([[1, 2]], np.int32), (65, 1))
+    bad_joint = coco.copy()
+    bad_joint[18, 1] = 18
+    calls = [
+        ('stages K=25', 'pp_decode_stages', stages(k=25)),
+        ('stages C=65', 'pp_decode_stages', stages(c=65, skel=wide)),
+        ('stages ann_capacity=0', 'pp_decode_stages', stages(cap=0)),
+        ('stages occupancy_reduction=0', 'pp_decode_stages',
+         stages(config=cfg(occupancy_reduction=0))),
+        ('stages skeleton index K+1', 'pp_decode_stages', stages(skel=bad_joint)),
+        ('stages NULL cif', 'pp_decode_stages', stages(cif=None)),
+        ('stages NULL workspace', 'pp_decode_stages', stages(ws=None)),
+        ('stages H=0', 'pp_decode_stages', stages(h=0)),
+        ('stages connection_method=2', 'pp_decode_stages',
+         stages(config=cfg(connection_method=2))),
+        ('stages workspace_bytes=16', 'pp_decode_stages', stages()),
+        ('stages n_img=0', 'pp_decode_stages', stages(n=0)),
+        ('stages n_img=-1', 'pp_decode_stages', stages(n=-1)),
+        ('stages K=25 and NULL skeleton', 'pp_decode_stages', stages(k=25, skel=None)),
+        ('stages K=25 and connection_method=2', 'pp_decode_stages',
+         stages(k=25, config=cfg(connection_method=2))),
+        ('batch C=65', 'pp_decode_batch', batch(c=65, skel=wide)),
+        ('batch NULL caf', 'pp_decode_batch', batch(caf=None)),
+        ('batch workspace_bytes=16', 'pp_decode_batch', batch()),
+        ('batch n_img=0', 'pp_decode_batch', batch(n=0)),
+        ('multi odd heads in pairs', 'pp_decode_multi', multi(arr=odd, pairs=1)),
+        ('multi NULL CIF field', 'pp_decode_multi', multi(arr=no_cif)),
+        ('multi K=25', 'pp_decode_multi', multi(k=25)),
+        ('multi skeleton index K+1', 'pp_decode_multi', multi(skel=bad_joint)),
+        ('multi workspace_bytes=16', 'pp_decode_multi', multi()),
+        ('multi n_img=0', 'pp_decode_multi', multi(n=0)),
+        ('initial odd heads in pairs', 'pp_decode_initial', initial(arr=odd, pairs=1)),
+        ('initial without counts', 'pp_decode_initial', initial(init_counts=None)),
+        ('initial counts alone', 'pp_decode_initial', initial(init=None)),
+        ('initial_capacity=0', 'pp_decode_initial', initial(init_cap=0)),
+        ('initial C=65', 'pp_decode_initial', initial(c=65, skel=wide)),
+        ('initial workspace_bytes=16', 'pp_decode_initial', initial()),
+        ('initial n_img=0', 'pp_decode_initial', initial(n=0)),
+        ('ragged NULL extents', 'pp_decode_ragged', ragged(d_extents=None)),
+        ('ragged d_cifhr', 'pp_decode_ragged', ragged(hr=p)),
+        ('ragged H=0', 'pp_decode_ragged', ragged(h=0)),
+        ('ragged negative threshold', 'pp_decode_ragged',
+         ragged(config=cfg(caf_threshold=-0.5))),
+        ('ragged extent outside', 'pp_decode_ragged', ragged(extents=((8, 9),))),
+        ('ragged extent 0', 'pp_decode_ragged', ragged(extents=((8, 8), (0, 3)), n=2)),
+        ('ragged K=25', 'pp_decode_ragged', ragged(k=25)),
+        ('ragged workspace_bytes=16', 'pp_decode_ragged', ragged()),
+        ('ragged n_img=0', 'pp_decode_ragged', ragged(n=0, extents=((8, 8),))),
+    ]
+    return calls, keep
+
+
+def _decode_refusals(lib):
+    """(label, status, pp_last_error() or None for PP_OK) of every _decode_refusal_calls entry"""
+    calls, keep = _decode_refusal_calls()
+    out = []
+    for label, name, args in calls:
+        rc = getattr(lib, name)(*args)
+        out.append((label, rc, lib.pp_last_error().decode() if rc else None))
+    del keep
+    return out
+
+
+def test_decode_refusals_pinned(lib):
+    """Every refusal of the five decode entry points, with its status and message as recorded
+    from the library before decode_heads' checks became check_decode: the same checks in the
+    same order (two cases trip two checks at once), the messages byte for byte (they name
+    pp_decode_batch whichever entry point was called).  Every refusal happens before any HIP
+    call, so no GPU is needed; an empty batch is PP_OK."""
+    got = _decode_refusals(lib)
+    assert [g[0] for g in got] == [r[0] for r in DECODE_REFUSALS]
+    for g, want in zip(got, DECODE_REFUSALS):
+        assert g == want
+
+
+_ENVELOPE = ('pp_decode_batch: shape outside the supported envelope '
+             '(K <= PP_MAX_KP, C <= PP_MAX_EDGES)')
+DECODE_REFUSALS = [
+    ('stages K=25', -2, _ENVELOPE),
+    ('stages C=65', -2, _ENVELOPE),
+    ('stages ann_capacity=0', -2, _ENVELOPE),
+    ('stages occupancy_reduction=0', -2, _ENVELOPE),
+    ('stages skeleton index K+1', -1, 'pp_decode_batch: skeleton joint index out of 1..K'),
+    ('stages NULL cif', -1, 'pp_decode_batch: NULL argument'),
+    ('stages NULL workspace', -1, 'pp_decode_batch: NULL argument'),
+    ('stages H=0', -2, 'pp_decode_batch: bad shape'),
+    ('stages connection_method=2', -1, 'connection method not known'),
+    ('stages workspace_bytes=16', -5, 'pp_decode_batch: workspace too small'),
+    ('stages n_img=0', 0, None),
+    ('stages n_img=-1', -2, _ENVELOPE),
+    ('stages K=25 and NULL skeleton', -1, 'pp_decode_batch: NULL argument'),
+    ('stages K=25 and connection_method=2', -2, _ENVELOPE),
+    ('batch C=65', -2, _ENVELOPE),
+    ('batch NULL caf', -1, 'pp_decode_batch: NULL argument'),
+    ('batch workspace_bytes=16', -5, 'pp_decode_batch: workspace too small'),
+    ('batch n_img=0', 0, None),
+    ('multi odd heads in pairs', -2,
+     'pp_decode_multi: CIF head count is not a multiple of the CifHr group size'),
+    ('multi NULL CIF field', -1, 'pp_decode_batch: NULL CIF field'),
+    ('multi K=25', -2, _ENVELOPE),
+    ('multi skeleton index K+1', -1, 'pp_decode_batch: skeleton joint index out of 1..K'),
+    ('multi workspace_bytes=16', -5, 'pp_decode_batch: workspace too small'),
+    ('multi n_img=0', 0, None),
+    ('initial odd heads in pairs', -2,
+     'pp_decode_initial: CIF head count is not a multiple of the CifHr group size'),
+    ('initial without counts', -1, 'pp_decode_initial: d_initial and d_initial_counts go together'),
+    ('initial counts alone', -1, 'pp_decode_initial: d_initial and d_initial_counts go together'),
+    ('initial_capacity=0', -2, 'pp_decode_initial: bad initial_capacity'),
+    ('initial C=65', -2, _ENVELOPE),
+    ('initial workspace_bytes=16', -5, 'pp_decode_batch: workspace too small'),
+    ('initial n_img=0', 0, None),
+    ('ragged NULL extents', -1, 'pp_decode_ragged: NULL argument'),
+    ('ragged d_cifhr', -1,
+     'pp_decode_ragged: the dense CifHr map of a ragged batch has no layout '
+     '(d_cifhr must be NULL)'),
+    ('ragged H=0', -2, 'pp_decode_ragged: bad shape'),
+    ('ragged negative threshold', -1, 'pp_decode_ragged: a ragged batch needs thresholds >= 0'),
+    ('ragged extent outside', -2, 'pp_decode_ragged: extent outside the container'),
+    ('ragged extent 0', -2, 'pp_decode_ragged: extent outside the container'),
+    ('ragged K=25', -2, _ENVELOPE),
+    ('ragged workspace_bytes=16', -5, 'pp_decode_batch: workspace too small'),
+    ('ragged n_img=0', 0, None),
+]
+
+
 def test_packed_record_size_matches_python_layout():
     """pp_packed_record_size (a host function) agrees with _abi.packed_dtype for every flag
     set, COCO and dense skeletons; compact records are at least 2x smaller than pp_ann."""

@@ -172,6 +172,28 @@ def test_batch_vs_oracle(dec, name, n, ext):
     assert offsets[-1] >= 2 * n
 
 
+def test_repeated_pairs_batch_vs_oracle(dec):
+    """kc.REPEATED (an unordered pair twice: a later by_source entry overwrites the earlier
+    one in place, csrc/by_source.hpp through decode.hip's grow_args) as 3-image uniform 20x23
+    eval batches, so seed_loop_ext_kernel runs: every image the oracle's bytes, twice."""
+    assert _ext_workgroups(3) == 3
+    cfg = kc.config('eval')
+    gu.configure_decoder(dec, _mode('eval'))
+    for name, (k, skeleton) in sorted(kc.REPEATED.items()):
+        cif, caf = kc.uniform_kc_batch(k, len(skeleton), 3, 20, 23, first_seed=0)
+        refs = [oracle.decode(cif[i], caf[i], skeleton, cfg) for i in range(3)]
+        assert len(refs[0]) == {'rep3': 5, 'rep4': 9}[name]
+        cc = dec.CifCaf(dec.FieldConfig(), keypoints=kc.keypoint_names(k), skeleton=skeleton)
+        for run in range(2):
+            recs, offsets, _ = cc.decode_records(cif, caf)
+            for i, ref in enumerate(refs):
+                got = recs[offsets[i]:offsets[i + 1]]
+                assert len(got) == len(ref), (name, run, i, len(got), len(ref))
+                for key in KEYS:
+                    assert got[key].tobytes() == ref[key].tobytes(), (name, run, i, key)
+                assert (got['image'] == i).all()
+
+
 # ---- d. variants -----------------------------------------------------------------------------
 
 @pytest.mark.parametrize('gen,mode', [('uniform', 'eval'), ('planted', 'eval'),

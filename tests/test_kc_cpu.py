@@ -174,6 +174,31 @@ def test_twin_vs_oracle_batch(name):
         assert got.tobytes() == ref.tobytes()
 
 
+@pytest.mark.parametrize('name', sorted(kc.REPEATED))
+def test_twin_vs_oracle_repeated_pairs(name):
+    """Skeletons with an unordered pair twice (kc.REPEATED): a later duplicate by_source key
+    overwrites the CAF index and direction in place.  The only test that reaches that branch
+    of csrc/by_source.hpp; uniform fields in eval defaults (predict defaults decode nothing
+    on them)."""
+    k, skeleton = kc.REPEATED[name]
+    with pytest.raises(AssertionError):
+        kc.check_skeleton(k, skeleton)
+    cfg = kc.config('eval')
+    counts = []
+    longest = 0
+    for h, w, seed in ((20, 23, 0), (12, 15, 5)):
+        cif, caf = kc.uniform_kc(k, len(skeleton), h, w, seed)
+        ref = oracle.decode(cif, caf, skeleton, cfg)
+        got, _ = stages_cpu.decode_batch(cif[None], caf[None], skeleton, cfg, n_threads=1)
+        _same(got, ref)
+        counts.append(len(ref))
+        longest = max(longest, int(ref['n_frontier'].max()))
+    # what the oracle alone decodes there, so that the comparison is not vacuous
+    assert counts == {'rep3': [5, 3], 'rep4': [9, 2]}[name]
+    if name == 'rep4':
+        assert longest == 5
+
+
 def variant_configs(name):
     """The option sets of the `variants` tests: name -> pp_config keyword arguments."""
     k, skeleton = kc.case(name)
