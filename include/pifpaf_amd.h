@@ -747,6 +747,8 @@ size_t pp_decode_workspace_zero_offset(int32_t n_img, int32_t K, int32_t C, int3
  * because the reference's scalar_values bounds, its splat box clip and its occupancy grid
  * follow the image's own CifHr size.  Everything else (workspace, capacities, outputs,
  * status bits, stage mask) is pp_decode_stages' at the container's (H, W).
+ * pp_cifdet_decode_ragged (below) is the detection decoder over the same kind of batch, a
+ * container (n_img, K, 7, H, W) with the same extent table.
  *
  * pp_fields_pack_ragged builds one container: `fields` is a HOST array of n_img device
  * pointers, image i's contiguous float32 (n_fields, channels, h_i, w_i), and `extents` the
@@ -778,6 +780,32 @@ int pp_decode_ragged(const float *d_cif, const float *d_caf, int32_t n_img, int3
                      float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
                      int32_t *d_status, void *d_workspace, size_t workspace_bytes,
                      uint32_t stages, void *stream);
+/*
+ * pp_cifdet_decode_ragged: pp_cifdet_decode over a ragged batch, one detection head without a
+ * min scale.  d_det is the container (n_img, K, 7, H, W) (pp_fields_pack_ragged with channels
+ * 7, or pp_fields_from_conv_ragged with layout 2, CifDet), d_extents / extents the device and
+ * host tables as pp_decode_ragged takes them.  Image i's records are, bit for bit, those of
+ * pp_cifdet_decode of the image alone at its own size; pp_det.image is its position in the
+ * batch.  The image's own CifHr size decides the splat box clip of CifDetHr.accumulate
+ * (cif_hr.py:84-100), the bounds of scalar_values in CifDetSeeds.fill_cif
+ * (cif_seeds.py:67-90) and Occupancy(cifhr.shape, 2, min_scale=2.0) (cifdet.py:38-45);
+ * workspace (pp_cifdet_ragged_workspace_size), capacities, outputs and status bits are
+ * pp_cifdet_decode's at the container's (H, W).
+ * d_cifhr (optional) receives the dense map (n_img, K, (H - 1) * stride + 1, pitch) at the
+ * container's size: image i's own map in the top-left H'_i x W'_i of its planes, +0.0f in
+ * every other element.
+ * PP_ESHAPE: an extent <= 0 or larger than the container.  PP_EINVAL: a negative
+ * cif_threshold or seed_threshold (cells outside an extent must pass no `c > threshold`).
+ * Every argument error is returned before any launch.
+ */
+size_t pp_cifdet_ragged_workspace_size(int32_t n_img, int32_t K, int32_t H, int32_t W,
+                                       const pp_config *cfg, int32_t det_capacity);
+int pp_cifdet_decode_ragged(const float *d_det, int32_t n_img, int32_t K, int32_t H, int32_t W,
+                            const int32_t *d_extents, const int32_t *extents,
+                            const pp_config *cfg, const pp_det_nms *nms, float *d_cifhr,
+                            pp_det *d_out, int32_t det_capacity, int32_t *d_counts,
+                            int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                            void *stream);
 
 /* ---------------------------------------------------------------------------------
  * openpifpaf.functional primitives (functional.pyx).  `field` arguments are

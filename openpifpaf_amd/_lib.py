@@ -167,6 +167,9 @@ _SIGNATURES = {
                               ctypes.c_int),
     'pp_decode_ragged': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                           _i32, _vp, _vp, _vp, _sz, _u32, _vp], ctypes.c_int),
+    'pp_cifdet_ragged_workspace_size': ([_i32, _i32, _i32, _i32, _vp, _i32], _sz),
+    'pp_cifdet_decode_ragged': ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                 _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
     'pp_decode_ragged_cpu': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
                               _vp, _vp, _i32], ctypes.c_int),
 }

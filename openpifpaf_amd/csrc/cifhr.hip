@@ -382,8 +382,19 @@ struct HrSplatArgs {
     int tiles_x, tiles, tiles_y;
 };
 
+// `ext` (hr_dims): NULL, or the images' own field sizes (cifhr_splats_ragged_kernel): a splat's
+// box is clipped to the image's own map (scalar_square_add_gauss_with_max's bounds are the
+// field's, functional.pyx:122-129).  cifhr_tile_kernel folds every pixel of the container's
+// map, so past an image's own right or bottom edge the fast fold's "pixels past the map's
+// edge never fold" (box_in_circle) does not hold: the pixels there are on the container's
+// map, and a splat whose centre lies beyond the edge reaches them although the first pixel
+// past the edge fails the circle test.  A candidate whose box ends at the image's own right
+// or bottom edge therefore takes the slow path, which tests the box; every other box ends
+// where the circle does, and box_in_circle checks it against the container's size.
+// The arguments are taken by value: by reference the uniform DET kernel came out at 74
+// VGPRs and 6 waves per SIMD instead of 68 and 7 (DESIGN.md §4 "Ragged CifDet").
 template <bool DET>
-__global__ __launch_bounds__(256) void cifhr_splats_kernel(HrSplatArgs a) {
+__device__ __forceinline__ void cifhr_splats_body(const HrSplatArgs a, const int32_t *ext) {
     __shared__ int s_tmp[4];
     __shared__ RowBinLds s_rb;
     __shared__ uint32_t s_bits[kTileBits / 32];
@@ -393,6 +404,7 @@ __global__ __launch_bounds__(256) void cifhr_splats_kernel(HrSplatArgs a) {
     const int ng = a.h.n_groups;
     const int64_t fld = blockIdx.x / ng;  // image * K + field
     const int g = (int)(blockIdx.x % ng);
+    const HrDims dm = hr_dims(ext, ext ? fld / a.K : 0, a.h.cstride[0], a.hh, a.ww);
     const float stride = (float)a.h.cstride[g];
     const bool ms_on = (a.h.ms_on >> g) & 1u;
     const float ms_th = a.h.ms_th[g];
@@ -444,8 +456,10 @@ __global__ __launch_bounds__(256) void cifhr_splats_kernel(HrSplatArgs a) {
                     }
                     const float sigma = (sg != sg) ? sg : fmaxf(1.0f, sg);  // np.maximum keeps NaN
                     const float v = (c[k] / a.neighbors) / len_cifs;        // v / neighbors / len_cifs
-                    const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, a.hh, a.ww);
-                    out[running + slot] = make_cand(box, make_float4(cx, cy, v, sigma * sigma), a.hh, a.ww);
+                    const int4 box = splat_box<M_GAUSS_MAX>(cx, cy, 1.0f * sigma, dm.hh, dm.ww);
+                    FoldCand fc = make_cand(box, make_float4(cx, cy, v, sigma * sigma), a.hh, a.ww);
+                    if (ext && (box.y == dm.ww || box.w == dm.hh)) fc.r = 0.0f;  // cand_slow
+                    out[running + slot] = fc;
                     if (use_bits) {  // mark the 64x64 output tiles this splat's box touches
                         for (int ty = box.z / kTile; ty <= (box.w - 1) / kTile; ty++)
                             for (int tx = box.x / kTile; tx <= (box.y - 1) / kTile; tx++) {
@@ -468,6 +482,16 @@ __global__ __launch_bounds__(256) void cifhr_splats_kernel(HrSplatArgs a) {
         hr_row_bins(out, running, a.bins + (int64_t)blockIdx.x * a.bins_cap, a.bins_cap,
                     a.tiles_y, s_rb, a.rowcnt + (int64_t)blockIdx.x * kMaxBinRows,
                     a.rowoff + (int64_t)blockIdx.x * kMaxBinRows);
+}
+
+template <bool DET>
+__global__ __launch_bounds__(256) void cifhr_splats_kernel(HrSplatArgs a) {
+    cifhr_splats_body<DET>(a, nullptr);
+}
+
+template <bool DET>
+__global__ __launch_bounds__(256) void cifhr_splats_ragged_kernel(HrSplatArgs a, const int32_t *ext) {
+    cifhr_splats_body<DET>(a, ext);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1698,11 +1722,13 @@ size_t cifhr_heads_workspace_size(const Heads &h, int n_img, int K) {
 template <bool DET>
 int cifhr_heads_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config *cfg,
                        float *d_cifhr, void *d_workspace, size_t workspace_bytes, hipStream_t s,
-                       const char *who) {
+                       const char *who, const int32_t *ext) {
     if (!cfg || !d_cifhr || !d_workspace) return fail(PP_EINVAL, std::string(who) + ": NULL argument");
     for (int m = 0; m < h.n_cif; m++)
         if (!h.cif[m]) return fail(PP_EINVAL, std::string(who) + ": NULL field");
     if (n_img < 0 || K <= 0) return fail(PP_ESHAPE, std::string(who) + ": bad shape");
+    if (ext && (!DET || h.n_cif != 1 || h.n_groups != 1 || h.group_size() != 1 || h.ms_on))
+        return fail(PP_EINVAL, std::string(who) + ": a ragged batch has one detection head and no min scale");
     if (n_img == 0) return PP_OK;
     if (workspace_bytes < cifhr_heads_workspace_size(h, n_img, K))
         return fail(PP_ENOMEM, std::string(who) + ": workspace too small");
@@ -1758,6 +1784,9 @@ int cifhr_heads_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config
         la.pre_rowoff = sa.rowoff;
         if (sa.tiles > kTileBits) return fail(PP_ESHAPE, std::string(who) + ": CifHr map too large");
         hipLaunchKernelGGL(cifhr_list_kernel<false>, dim3((unsigned)nf), dim3(256), 0, s, la);
+    } else if (ext) {
+        if constexpr (DET)  // (refused above otherwise: no CifHr instance of the ragged kernel)
+            hipLaunchKernelGGL(cifhr_splats_ragged_kernel<true>, dim3((unsigned)(nf * h.n_groups)), dim3(256), 0, s, sa, ext);
     } else {
         hipLaunchKernelGGL(cifhr_splats_kernel<DET>, dim3((unsigned)(nf * h.n_groups)), dim3(256), 0, s, sa);
     }
@@ -1792,9 +1821,9 @@ int cifhr_heads_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config
 }
 
 template int cifhr_heads_launch<false>(const Heads &, int32_t, int32_t, const pp_config *, float *,
-                                       void *, size_t, hipStream_t, const char *);
+                                       void *, size_t, hipStream_t, const char *, const int32_t *);
 template int cifhr_heads_launch<true>(const Heads &, int32_t, int32_t, const pp_config *, float *,
-                                      void *, size_t, hipStream_t, const char *);
+                                      void *, size_t, hipStream_t, const char *, const int32_t *);
 
 // workgroups per field of cifhr_sparse_kernel: fewer fields than kSplitSlots split each
 // field's tiles over several workgroups (each builds its own copy of the field's list: a

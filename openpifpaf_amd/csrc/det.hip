@@ -11,6 +11,9 @@
 //   det_output_kernel          per image: kept seeds merged into the global seed order,
 //                              AnnotationDet boxes, nms.Detection (nms.py:79-102) in float32
 //                              as NumPy evaluates it, output records
+// pp_cifdet_decode_ragged decodes images of different field sizes in one batch: the seeds and
+// select kernels (and cifhr.hip's splats kernel) are bodies over a nullable extent table
+// (hr_dims), the old kernel names pass NULL (DESIGN.md §4 "Ragged CifDet").
 #include "pp_common.hpp"
 
 #include <math.h>
@@ -32,7 +35,8 @@ struct DetArgs {
     // per (image, field) segments: v, x, y, w, h (each `cells`) and counts
     float *seg;
     int *seg_n;
-    uint64_t *gkeys;       // (n_img * K, cells) global sort keys beyond kDetSortLds
+    uint64_t *gkeys;       // (n_img * K, det_key_stride(cells)) global sort keys beyond
+                           // kDetSortLds
     int2 *gbox;            // (n_img * K, cells) boxes beyond kDetBoxLds
     int *kept;             // (n_img * K, cells) kept seeds (emission indices), in sorted order
     int *kept_n;
@@ -53,11 +57,14 @@ __device__ __forceinline__ int64_t seg_base(const DetArgs &a, int64_t fld) {
 }
 
 // CifDetSeeds.fill (cif_seeds.py:56-64 over the heads, 67-90 per head) for one field: the
-// heads in order, each one's cells in row-major order, appended to the field's segment
-__global__ __launch_bounds__(256) void det_seeds_emit_kernel(DetArgs a) {
+// heads in order, each one's cells in row-major order, appended to the field's segment.
+// `ext` (hr_dims): NULL, or the images' own field sizes (det_seeds_emit_ragged_kernel): the
+// bounds of scalar_values (cif_seeds.py:83) are those of the image's own map.
+__device__ __forceinline__ void det_seeds_emit_body(const DetArgs &a, const int32_t *ext) {
     __shared__ int s_tmp[4];
     const int64_t fld = blockIdx.x;
     const int img = (int)(fld / a.K), f = (int)(fld % a.K);
+    const HrDims dm = hr_dims(ext, img, a.hd.cstride[0], a.hh, a.ww);
     const int64_t cells = a.cells;
     const float *t = a.hr + ((int64_t)img * a.K + f) * a.hh * a.pitch;
     float *sv = a.seg + seg_base(a, fld), *sx = sv + cells, *sy = sx + cells, *sw = sy + cells,
@@ -81,7 +88,7 @@ __global__ __launch_bounds__(256) void det_seeds_emit_kernel(DetArgs a) {
                 if (c > a.th && (!ms_on || (p[4 * hw + cell] > ms_th && p[5 * hw + cell] > ms_th))) {
                     x = p[hw + cell] * stride;
                     y = p[2 * hw + cell] * stride;
-                    const float hv = hr_lookup(t, a.hh, a.ww, a.pitch, x, y, 0.0f);
+                    const float hv = hr_lookup(t, dm.hh, dm.ww, a.pitch, x, y, 0.0f);
                     v = 0.9f * hv + 0.1f * c;
                     if (a.score_scale != 1.0f) v = v * a.score_scale;
                     keep = v > a.th;
@@ -103,6 +110,14 @@ __global__ __launch_bounds__(256) void det_seeds_emit_kernel(DetArgs a) {
         }
     }
     if (threadIdx.x == 0) a.seg_n[fld] = running;
+}
+
+__global__ __launch_bounds__(256) void det_seeds_emit_kernel(DetArgs a) {
+    det_seeds_emit_body(a, nullptr);
+}
+
+__global__ __launch_bounds__(256) void det_seeds_emit_ragged_kernel(DetArgs a, const int32_t *ext) {
+    det_seeds_emit_body(a, ext);
 }
 
 // Occupancy.set box (occupancy.py:31-39, utils.py:61-66) with reduction 2, min_scale 2.0
@@ -129,18 +144,34 @@ __device__ __forceinline__ bool box_covers(int2 b, int xi, int yi) {
 
 constexpr uint32_t kDetEmitMask = 0xFFFFFFFFu;
 
-// one field: sort (v desc, then x, y, w, h desc, then emission) and run the occupancy loop
-__global__ __launch_bounds__(256) void det_select_kernel(DetArgs a) {
+// keys per field of the global sort (DetArgs::gkeys): the bitonic network runs over the next
+// power of two >= the field's seeds, which is at most the next power of two >= its cells
+__host__ __device__ inline int64_t det_key_stride(int64_t cells) {
+    int64_t s = 1;
+    while (s < cells) s <<= 1;
+    return s;
+}
+
+// one field: sort (v desc, then x, y, w, h desc, then emission) and run the occupancy loop.
+// `ext` (hr_dims): NULL, or the images' own field sizes (det_select_ragged_kernel): the
+// occupancy grid is Occupancy(cifhr.shape, 2, ...) of the image's own map (cifdet.py:38).
+__device__ __forceinline__ void det_select_body(const DetArgs &a, const int32_t *ext) {
     __shared__ uint64_t s_key[kDetSortLds];
     __shared__ int2 s_box[kDetBoxLds];
     const int64_t fld = blockIdx.x;
     const int hw = a.cells;
+    int oh = a.oh, ow = a.ow;
+    if (ext) {  // int(H' / 2.0), int(W' / 2.0)
+        const HrDims dm = hr_dims(ext, fld / a.K, a.hd.cstride[0], a.hh, a.ww);
+        oh = dm.hh / 2;
+        ow = dm.ww / 2;
+    }
     const int n = a.seg_n[fld];
     const float *sv = a.seg + seg_base(a, fld), *sx = sv + hw, *sy = sx + hw, *sw = sy + hw,
                 *sh = sw + hw;
     int np = 1;
     while (np < n) np <<= 1;
-    uint64_t *key = np <= kDetSortLds ? s_key : a.gkeys + fld * (int64_t)hw;
+    uint64_t *key = np <= kDetSortLds ? s_key : a.gkeys + fld * det_key_stride(hw);
     // seeds have v > threshold >= 0: float order == integer order of the bits
     for (int i = threadIdx.x; i < np; i += 256)
         key[i] = i < n ? ((uint64_t)__float_as_uint(sv[i]) << 32) | (kDetEmitMask - (uint32_t)i) : 0;
@@ -207,10 +238,10 @@ __global__ __launch_bounds__(256) void det_select_kernel(DetArgs a) {
             w = sw[e];
             h = sh[e];
         }
-        bool fixed_free = a.oh <= 0 || a.ow <= 0;  // the reference reads out of bounds here
+        bool fixed_free = oh <= 0 || ow <= 0;  // the reference reads out of bounds here
         if (!fixed_free) {
-            xi = (int)clip_ref(x / 2.0f, 0.0f, (float)(a.ow - 1));
-            yi = (int)clip_ref(y / 2.0f, 0.0f, (float)(a.oh - 1));
+            xi = (int)clip_ref(x / 2.0f, 0.0f, (float)(ow - 1));
+            yi = (int)clip_ref(y / 2.0f, 0.0f, (float)(oh - 1));
         }
         int cnt = 0;
         for (int q = 0; q < nbox; q++) cnt += box_covers(boxes[q], xi, yi);
@@ -226,7 +257,7 @@ __global__ __launch_bounds__(256) void det_select_kernel(DetArgs a) {
             nk++;
             const float mwh = bh < bw ? bh : bw;  // builtin min(w, h)
             int2 b;
-            if (!fixed_free && det_box(a.ow, a.oh, bx, by, 0.1f * mwh, b)) {
+            if (!fixed_free && det_box(ow, oh, bx, by, 0.1f * mwh, b)) {
                 if (lane == 0) boxes[nbox] = b;
                 nbox++;
                 cnt += box_covers(b, xi, yi);
@@ -237,6 +268,12 @@ __global__ __launch_bounds__(256) void det_select_kernel(DetArgs a) {
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) a.kept_n[fld] = nk;
+}
+
+__global__ __launch_bounds__(256) void det_select_kernel(DetArgs a) { det_select_body(a, nullptr); }
+
+__global__ __launch_bounds__(256) void det_select_ragged_kernel(DetArgs a, const int32_t *ext) {
+    det_select_body(a, ext);
 }
 
 // NumPy's float32 np.maximum / np.minimum (NaN propagates)
@@ -500,7 +537,7 @@ static DetLayout det_layout(const Heads &h, int n_img, int K, int cap) {
     d.off_hr_ws = take(d.hr_ws);
     d.off_seg = take(nf * 5 * cells * sizeof(float));
     d.off_seg_n = take(nf * sizeof(int));
-    d.off_keys = take(nf * cells * sizeof(uint64_t));
+    d.off_keys = take(nf * (size_t)det_key_stride((int64_t)cells) * sizeof(uint64_t));
     d.off_box = take(nf * cells * sizeof(int2));
     d.off_kept = take(nf * cells * sizeof(int));
     d.off_kept_n = take(nf * sizeof(int));
@@ -549,7 +586,7 @@ static int det_decode_launch(const Heads &h, int32_t n_img, int32_t K, const pp_
                              const pp_det_nms *nms, float *d_cifhr, pp_det *d_out,
                              int32_t det_capacity, int32_t *d_counts, int32_t *d_status,
                              void *d_workspace, size_t workspace_bytes, hipStream_t s,
-                             const char *who) {
+                             const char *who, const int32_t *ext = nullptr) {
     if (!cfg || !nms || !d_out || !d_counts || !d_status || !d_workspace)
         return fail(PP_EINVAL, std::string(who) + ": NULL argument");
     for (int m = 0; m < h.n_cif; m++)
@@ -566,7 +603,7 @@ static int det_decode_launch(const Heads &h, int32_t n_img, int32_t K, const pp_
     if (hh >= 65535 || ww >= 65535) return fail(PP_ESHAPE, std::string(who) + ": field too large");
     char *ws = (char *)d_workspace;
     float *hr = d_cifhr ? d_cifhr : (float *)(ws + d.off_hr);
-    int rc = cifhr_heads_launch<true>(h, n_img, K, cfg, hr, ws + d.off_hr_ws, d.hr_ws, s, who);
+    int rc = cifhr_heads_launch<true>(h, n_img, K, cfg, hr, ws + d.off_hr_ws, d.hr_ws, s, who, ext);
     if (rc) return rc;
     DetArgs a = det_seed_args(h, hr, K, cfg, (float *)(ws + d.off_seg), (int *)(ws + d.off_seg_n));
     a.gkeys = (uint64_t *)(ws + d.off_keys);
@@ -584,8 +621,13 @@ static int det_decode_launch(const Heads &h, int32_t n_img, int32_t K, const pp_
     a.counts = d_counts;
     a.status = d_status;
     const unsigned nf = (unsigned)((int64_t)n_img * K);
-    hipLaunchKernelGGL(det_seeds_emit_kernel, dim3(nf), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(det_select_kernel, dim3(nf), dim3(256), 0, s, a);
+    if (ext) {
+        hipLaunchKernelGGL(det_seeds_emit_ragged_kernel, dim3(nf), dim3(256), 0, s, a, ext);
+        hipLaunchKernelGGL(det_select_ragged_kernel, dim3(nf), dim3(256), 0, s, a, ext);
+    } else {
+        hipLaunchKernelGGL(det_seeds_emit_kernel, dim3(nf), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(det_select_kernel, dim3(nf), dim3(256), 0, s, a);
+    }
     hipLaunchKernelGGL(det_output_kernel, dim3((unsigned)n_img), dim3(256), 0, s, a);
     return check_launch(who);
 }
@@ -673,6 +715,39 @@ int pp_cifdet_decode(const float *d_det, int32_t n_img, int32_t K, int32_t H, in
     return det_decode_launch(single_head(d_det, nullptr, H, W, cfg->stride), n_img, K, cfg, nms,
                              d_cifhr, d_out, det_capacity, d_counts, d_status, d_workspace,
                              workspace_bytes, (hipStream_t)stream, "pp_cifdet_decode");
+}
+
+size_t pp_cifdet_ragged_workspace_size(int32_t n_img, int32_t K, int32_t H, int32_t W,
+                                       const pp_config *cfg, int32_t det_capacity) {
+    return pp_cifdet_workspace_size(n_img, K, H, W, cfg, det_capacity);
+}
+
+// a ragged batch: the kernels that read the map's size take the extent table (hr_dims);
+// tiles, pitch, segment capacity and every buffer are the container's
+int pp_cifdet_decode_ragged(const float *d_det, int32_t n_img, int32_t K, int32_t H, int32_t W,
+                            const int32_t *d_extents, const int32_t *extents,
+                            const pp_config *cfg, const pp_det_nms *nms, float *d_cifhr,
+                            pp_det *d_out, int32_t det_capacity, int32_t *d_counts,
+                            int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                            void *stream) {
+    const char *who = "pp_cifdet_decode_ragged";
+    if (!d_det || !cfg || !nms || !d_extents || !extents || !d_out || !d_counts || !d_status ||
+        !d_workspace)
+        return fail(PP_EINVAL, std::string(who) + ": NULL argument");
+    if (H <= 0 || W <= 0 || cfg->stride <= 0 || n_img < 0 || K <= 0 || K > 4096 ||
+        det_capacity <= 0)
+        return fail(PP_ESHAPE, std::string(who) + ": bad shape");
+    // cells outside an extent (confidence 0) must pass no `c > threshold`
+    if (!(cfg->cif_threshold >= 0.0f) || !(cfg->seed_threshold >= 0.0f))
+        return fail(PP_EINVAL, std::string(who) + ": cif_threshold and seed_threshold must be >= 0");
+    for (int32_t i = 0; i < n_img; i++)
+        if (extents[2 * i] <= 0 || extents[2 * i] > H || extents[2 * i + 1] <= 0 ||
+            extents[2 * i + 1] > W)
+            return fail(PP_ESHAPE, std::string(who) + ": extent of image " + std::to_string(i) +
+                                       " is empty or larger than the container");
+    return det_decode_launch(single_head(d_det, nullptr, H, W, cfg->stride), n_img, K, cfg, nms,
+                             d_cifhr, d_out, det_capacity, d_counts, d_status, d_workspace,
+                             workspace_bytes, (hipStream_t)stream, who, d_extents);
 }
 
 size_t pp_cifdet_multi_workspace_size(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,

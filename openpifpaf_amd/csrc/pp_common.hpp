@@ -492,11 +492,13 @@ Heads single_head(const float *cif, const float *caf, int H, int W, int stride);
 
 // stage launchers over heads (cifhr.hip, stages.hip)
 size_t cifhr_heads_workspace_size(const Heads &h, int n_img, int K);
-// dense (n_img * K, hh, pitch) map, every pixel written
+// dense (n_img * K, hh, pitch) map, every pixel written; `ext` (NULL: none): a ragged
+// detection batch's extent table (hr_dims; DET, one head, no min scale): image i's own map in
+// the top-left corner of its planes, +0 elsewhere
 template <bool DET>
 int cifhr_heads_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config *cfg,
                        float *d_cifhr, void *d_workspace, size_t workspace_bytes, hipStream_t s,
-                       const char *who);
+                       const char *who, const int32_t *ext = nullptr);
 // the decoder's block-sparse scratch map (HrMap with masks): d_map (n_img * K, tiles, 64, 64),
 // d_masks (n_img * K, tiles); d_aux (same size as d_map) only when h.n_groups > 1
 size_t cifhr_sparse_workspace_size(const Heads &h, int n_img, int K);

@@ -2,8 +2,9 @@
 
 Same constructor and call signature as the reference.  One call runs CifDetHr, CifDetSeeds,
 the occupancy loop and nms.Detection on the device for one image (`__call__`) or a whole
-batch (`decode_batch`), configured from the CifHr / CifSeeds / nms.Detection class
-attributes as the reference's decoder.configure() sets them.
+batch (`decode_batch`), or for images of different field sizes as one batch
+(`decode_ragged`, `coco_ragged`; engine.RaggedDetFields), configured from the CifHr /
+CifSeeds / nms.Detection class attributes as the reference's decoder.configure() sets them.
 """
 import ctypes
 
@@ -14,6 +15,7 @@ from ... import _device
 from ..._abi import DET_DTYPE, DetNms, check_seed_mask, make_config, scale_list
 from ..._lib import PPError, call, load
 from ...annotation import AnnotationDet
+from ...engine import RaggedDetFields
 from .. import nms
 from ..cif_hr import CifHr
 from ..cif_seeds import CifSeeds
@@ -139,6 +141,84 @@ class CifDet(Generator):
                 raise PPError('CifDet: detection capacity overflow')
             cap = min(k * cells, 2 * cap)
         return out, counts
+
+    # -- ragged batches: images of different field sizes -----------------------------------
+    def _ragged(self, fields_list, kw):
+        """RaggedDetFields of a list of per-image head lists (each read through the
+        FieldConfig's one detection head), packed on the device."""
+        if kw.pop('group', None) is not None:
+            raise NotImplementedError('a ragged batch does not take group: its decode is '
+                                      'single-GPU (sharded ragged decode is not built)')
+        if kw:
+            raise TypeError('unexpected arguments: ' + ', '.join(sorted(kw)))
+        fc = self.field_config
+        if len(fc.cif_indices) != 1:
+            raise NotImplementedError('a ragged batch needs a FieldConfig with one detection '
+                                      'head, got {}; several heads are not built'.format(
+                                          len(fc.cif_indices)))
+        if fc.cif_min_scales[0]:
+            raise NotImplementedError('a ragged batch needs a FieldConfig without min scales; '
+                                      'min-scale masks over ragged extents are not built')
+        if isinstance(fields_list, RaggedDetFields):  # packed or ingested already
+            return fields_list
+        return RaggedDetFields([_device.to_device(f[fc.cif_indices[0]]) for f in fields_list])
+
+    def decode_ragged_device(self, ragged, cap=None):
+        """decode_device over a RaggedDetFields (pp_cifdet_decode_ragged), the workspace at the
+        container's shape: ((n, cap, record bytes) uint8, (n) int32 counts), complete."""
+        n, k, h, w = ragged.n, ragged.k, ragged.h, ragged.w
+        cfg = self.config()
+        z = det_nms_config()
+        cap = cap or max(64, h * w)
+        dev = ragged.det.device
+        while True:
+            size = int(load().pp_cifdet_ragged_workspace_size(n, k, h, w, ctypes.byref(cfg), cap))
+            if self._ws is None or self._ws.numel() < size or self._ws.device != dev:
+                self._ws = torch.empty(size, dtype=torch.uint8, device=dev)
+            out = torch.empty((n, cap, DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            call('pp_cifdet_decode_ragged', _device.ptr(ragged.det), n, k, h, w,
+                 _device.ptr(ragged.extents),
+                 ragged.extents_host.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cfg),
+                 ctypes.byref(z), _device.ptr(None), _device.ptr(out), cap, _device.ptr(counts),
+                 _device.ptr(status), _device.ptr(self._ws), ctypes.c_size_t(self._ws.numel()),
+                 _device.stream())
+            st = status.cpu().numpy()
+            if not (st & PP_ST_ANN_OVERFLOW).any():
+                break
+            if cap >= k * h * w:
+                raise PPError('CifDet: detection capacity overflow')
+            cap = min(k * h * w, 2 * cap)
+        return out, counts
+
+    def decode_ragged_records(self, fields_list, cap=None, **kw):
+        """decode_ragged up to the records: (pp_det records of all images, per-image
+        offsets); pp_det.image is the image's position in the batch."""
+        out, counts = self.decode_ragged_device(self._ragged(fields_list, kw), cap)
+        counts = counts.cpu().numpy().astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(counts)])
+        host = out.cpu().numpy()
+        recs = np.concatenate([host[i, :counts[i]].reshape(-1) for i in range(len(counts))])
+        return np.frombuffer(recs.tobytes(), dtype=DET_DTYPE), offsets
+
+    def decode_ragged(self, fields_list, **kw):
+        """One entry per image, each image's head outputs [det (K, 7, h_i, w_i), ...] at its
+        OWN size -> one list of AnnotationDet per image, each as __call__ gives it for that
+        image alone, decoded as one device batch (pp_cifdet_decode_ragged).  An
+        engine.RaggedDetFields (e.g. RaggedDetFields.from_conv, heads.RaggedDetCollector) in place of the list is decoded as it is."""
+        return self.annotations_from_records(*self.decode_ragged_records(fields_list, **kw))
+
+    def coco_ragged(self, fields_list, metas, **params):
+        """coco_batch for images of different field sizes (decode_ragged's `fields_list`)."""
+        from ...eval_coco import coco_records, metas_device  # pylint: disable=import-outside-toplevel
+        ragged = self._ragged(fields_list, {k: params.pop(k) for k in ('group',) if k in params})
+        if len(metas) != ragged.n:
+            raise ValueError('{} metas for {} images'.format(len(metas), ragged.n))
+        out, counts = self.decode_ragged_device(ragged)
+        d_metas, d_ids, _ = metas_device(metas, 0)
+        return coco_records(out, counts, d_metas, d_ids, det=True,
+                            k=params.pop('n_keypoints', 17), **params)
 
     def annotations_from_records(self, recs, offsets):
         return [[AnnotationDet.from_record(r, self.categories)

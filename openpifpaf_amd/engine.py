@@ -256,6 +256,81 @@ class RaggedFields:
                  ctypes.c_size_t(size), _device.stream())
 
 
+class RaggedDetFields:
+    """RaggedFields for the detection decoder (pp_cifdet_decode_ragged): `fields` is a list of
+    per-image CifDet device tensors, float32 and contiguous, (K, 7, h_i, w_i) with K the same
+    for every image.  Packs them on the current stream into the container `det`
+    (n, K, 7, H, W), (H, W) the largest size, zero outside each image's extent, and owns it
+    with the extent table (`extents`, device (n, 2) int32; `extents_host` the same on the
+    host).  The images' tensors may be freed once the pack has run.  A list of equal shapes
+    takes the same route.  RaggedDetFields.from_conv builds the same object from the head's
+    conv outputs, without per-image fields and without the pack."""
+
+    def __init__(self, fields):
+        lib = load()
+        fields = list(fields)
+        if not fields:
+            raise ValueError('a ragged batch needs at least one image')
+        for f in fields:
+            if not (isinstance(f, torch.Tensor) and _device.is_device(f) and
+                    f.dtype == torch.float32 and f.is_contiguous() and f.dim() == 4):
+                raise ValueError('ragged detection fields must be contiguous float32 device '
+                                 'tensors (K, 7, h, w)')
+            if f.shape[1] != 7:
+                raise ValueError('expected CifDet fields (K, 7, h, w) per image, got {}'.format(
+                    tuple(f.shape)))
+        self.n = n = len(fields)
+        self.k = fields[0].shape[0]
+        if any(f.shape[0] != self.k for f in fields):
+            raise ValueError('the images of a ragged batch differ in K: ' + ', '.join(
+                sorted({'K={}'.format(f.shape[0]) for f in fields})))
+        self.extents_host = np.array([f.shape[2:] for f in fields], np.int32).reshape(n, 2)
+        self.h, self.w = (int(v) for v in self.extents_host.max(axis=0))
+        dev = fields[0].device
+        self.det = torch.empty((n, self.k, 7, self.h, self.w), dtype=torch.float32, device=dev)
+        # pinned host tables (pointers, then extents): the copies are asynchronous, so the
+        # tables live as long as this object
+        size, ext_off = lib.pp_ragged_tables_size(n), lib.pp_ragged_extents_offset(n)
+        self._host = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        self._tables = torch.empty(size, dtype=torch.uint8, device=dev)
+        host = self._host.numpy()
+        host[:ext_off].view(np.uint64)[:] = [f.data_ptr() for f in fields]
+        host[ext_off:].view(np.int32)[:] = self.extents_host.reshape(-1)
+        self.extents = self._tables[ext_off:].view(torch.int32).view(n, 2)
+        self.pack()
+
+    _ingest = None  # from_conv: the head's heads.RaggedIngest
+
+    @classmethod
+    def from_conv(cls, convs, n_categories, quad=1, conv_extents=None, hflip=None):
+        """The same object from the detection head's conv outputs, one HIP pass straight into
+        the container (heads.fields_from_conv_ragged has the forms `convs` and `conv_extents`
+        take; `hflip`: heads.HFlip() for a mirrored pass): no per-image fields and no pack.
+        pack() runs the ingest launch again."""
+        from .heads import RaggedIngest  # pylint: disable=import-outside-toplevel
+        ingest = RaggedIngest(convs, n_categories, 'cifdet', quad, hflip, conv_extents)
+        self = cls.__new__(cls)
+        self.n, self.k, self.h, self.w = ingest.n, n_categories, ingest.h, ingest.w
+        self.det = ingest.out
+        self.extents, self.extents_host = ingest.extents, ingest.extents_host
+        self._ingest = ingest
+        self.pack()
+        return self
+
+    def pack(self):
+        """The pack launch on the current stream, from the tables built at construction: again
+        after the images' tensors were rewritten in place.  After from_conv: the ingest
+        launch."""
+        if self._ingest is not None:
+            self._ingest.launch()
+            return
+        size, ext_off = self._host.numel(), load().pp_ragged_extents_offset(self.n)
+        call('pp_fields_pack_ragged', ctypes.c_void_p(self._host.data_ptr()),
+             ctypes.c_void_p(self._host.data_ptr() + ext_off), self.n, self.k, 7, self.h, self.w,
+             _device.ptr(self.det), _device.ptr(self._tables), ctypes.c_size_t(size),
+             _device.stream())
+
+
 def _buffer_key(n, k, c, shape, cap, cfg):
     return (n, k, c, shape, cap, cfg.force_complete, cfg.stride, cfg.occupancy_reduction)
 

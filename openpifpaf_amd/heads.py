@@ -13,7 +13,8 @@ they lie, by their strides (pp_fields_from_conv_strided).
 `MultiScaleCollector` does that for the head list of a ShellMultiScale-style model
 (network/nets.py:95-143), whose second five scales come from the mirrored image.
 `fields_from_conv_ragged` / `RaggedCollector` ingest the conv outputs of images of different
-sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged).
+sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged);
+`RaggedDetCollector` does it for a detection head (engine.RaggedDetFields).
 """
 import ctypes
 
@@ -315,6 +316,21 @@ class RaggedCollector(torch.nn.Module):
         cif_convs, caf_convs = args[0]
         return RaggedFields.from_conv(cif_convs, caf_convs, self.n_cif, self.n_caf, self.quad,
                                       conv_extents=conv_extents)
+
+
+class RaggedDetCollector(torch.nn.Module):
+    """CifdetCollector for images of different sizes: forward((det_convs,),
+    conv_extents=None) -> engine.RaggedDetFields, the head ingested straight into its
+    container (the arguments are RaggedDetFields.from_conv's)."""
+
+    def __init__(self, n_categories, quad=1):
+        super().__init__()
+        self.n_categories, self.quad = n_categories, quad
+
+    def forward(self, *args, conv_extents=None):  # pylint: disable=arguments-differ
+        from .engine import RaggedDetFields  # pylint: disable=import-outside-toplevel
+        return RaggedDetFields.from_conv(args[0][0], self.n_categories, self.quad,
+                                         conv_extents=conv_extents)
 
 
 class CifCafCollector(torch.nn.Module):
