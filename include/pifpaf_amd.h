@@ -900,6 +900,54 @@ int pp_np_exp(const float *d_x, float *d_y, int64_t n, int32_t exp_mode, void *s
  */
 int pp_np_square(const float *d_x, float *d_y, int64_t n, void *stream);
 
+/*
+ * One query of pp_connection_values / pp_p2p_values: the source joint (x, y, v, s) = an
+ * annotation's data[start_i] and joint_scales[start_i]; for pp_p2p_values the target joint
+ * (tx, ty, ts) = target_xysv[:3]; `set` = the column set the query reads.
+ */
+typedef struct pp_edge_query {
+    float x, y, v, s;
+    float tx, ty, ts; /* unused by pp_connection_values */
+    int32_t set;
+} pp_edge_query;
+
+/*
+ * CifCaf.connection_value (cifcaf.py:194-217) for n_q queries in one launch, one wave per
+ * query, no host synchronisation.  Column sets: set i is a (9, d_counts[i]) array at
+ * d_cols + i * set_stride with row pitch `pitch` (set_stride >= 9 * pitch), i in
+ * [0, n_sets).  The (n_caf, 2, 9, cap) / (n_caf, 2) output of pp_caf_scored or
+ * pp_caf_scored_multi for one or many images is this layout without a copy: set_stride =
+ * 9 * cap, pitch = cap, set = ((image * n_caf) + caf_i) * 2 + direction, direction 1 =
+ * forward.  A query grows from (x, y) with scale max(0, s) over its set (caf_f,
+ * cifcaf.py:124-192 as pp_grow_connection), applies keypoint_threshold to sqrt(score * v)
+ * and the zero-score exit, and with reverse_match grows back from the new point over the
+ * opposite direction's set, set ^ 1 (caf_b; n_sets must then be even), testing the
+ * reverse result's SCALE against 0 as cifcaf.py:212 does, then the L1 distance against
+ * the source scale.  method as pp_grow_connection.  d_out = (n_q, 4) floats (x, y, scale,
+ * score), all zero where the reference returns its zero tuple.  A set index outside
+ * [0, n_sets) reads as an empty set and a count is held to [0, pitch] (the device entry
+ * cannot refuse what lies in device memory; the host twin returns PP_EINVAL for such an
+ * index).  n_q == 0 returns PP_OK without a launch.
+ */
+int pp_connection_values(const float *d_cols, int64_t set_stride, int64_t pitch,
+                         const int32_t *d_counts, int32_t n_sets, const pp_edge_query *d_queries,
+                         int64_t n_q, int32_t method, float keypoint_threshold,
+                         int32_t reverse_match, float *d_out, void *stream);
+
+/*
+ * CifCaf.p2p_value (cifcaf.py:219-245) for n_q queries in one launch; sets and queries as
+ * pp_connection_values (only method bit 1, the exp mode, matters).  Per column of the
+ * query's set inside the caf_center_s box of 2 * max(0, s) around (x, y): exp(-0.5 d_s^2
+ * / sigma_s^2) * exp(-0.5 d_t^2 / sigma_t^2) * v, sigma = 0.5 * max(0, scale); d_out[q] =
+ * sqrt(v * max(scores)), 0.0 when no column is kept.  max is Python's max() over the kept
+ * columns in column order (cifcaf.py:245): it keeps its first element unless a later one
+ * compares greater, so the result is NaN exactly when the first kept column's score is
+ * NaN, and a NaN score of any later column is ignored.  d_out = (n_q) floats.
+ */
+int pp_p2p_values(const float *d_cols, int64_t set_stride, int64_t pitch, const int32_t *d_counts,
+                  int32_t n_sets, const pp_edge_query *d_queries, int64_t n_q, int32_t method,
+                  float *d_out, void *stream);
+
 /* ---------------------------------------------------------------------------------
  * Host twins of the functional.pyx primitives above (SURVEY.md §8(b) `_cpu` variants):
  * the same arguments as the device entry points minus the stream, HOST pointers, run
@@ -941,6 +989,15 @@ int pp_occupancy_set_cpu(uint8_t *occ, int32_t n_planes, int64_t h, int64_t w, i
 int pp_center_filter_cpu(const float *field, int64_t rows, int64_t n, int64_t pitch, int32_t mode,
                          float x, float y, float sigma, void *out, int64_t out_pitch,
                          int32_t *count);
+/* pp_connection_values / pp_p2p_values (cifcaf.py:194-245) on host pointers, byte-identical
+ * with the kernels; a query whose set index lies outside [0, n_sets) is PP_EINVAL */
+int pp_connection_values_cpu(const float *cols, int64_t set_stride, int64_t pitch,
+                             const int32_t *counts, int32_t n_sets, const pp_edge_query *queries,
+                             int64_t n_q, int32_t method, float keypoint_threshold,
+                             int32_t reverse_match, float *out);
+int pp_p2p_values_cpu(const float *cols, int64_t set_stride, int64_t pitch, const int32_t *counts,
+                      int32_t n_sets, const pp_edge_query *queries, int64_t n_q, int32_t method,
+                      float *out);
 
 /* ---------------------------------------------------------------------------------
  * Host twins of the front stages (csrc/stages_cpu.hip): pp_cifhr / pp_seeds /

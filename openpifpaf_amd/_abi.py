@@ -70,6 +70,14 @@ SEED_DTYPE = np.dtype([
 ])
 
 
+# pp_edge_query: one query of pp_connection_values / pp_p2p_values
+EDGE_QUERY_DTYPE = np.dtype([
+    ('x', np.float32), ('y', np.float32), ('v', np.float32), ('s', np.float32),
+    ('tx', np.float32), ('ty', np.float32), ('ts', np.float32), ('set', np.int32),
+])
+assert EDGE_QUERY_DTYPE.itemsize == 32
+
+
 class PPConfig(ctypes.Structure):
     """struct pp_config (include/pifpaf_amd.h)."""
     _fields_ = [

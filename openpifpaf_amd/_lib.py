@@ -78,6 +78,13 @@ _SIGNATURES = {
     'pp_scalar_lookup': ([_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _f, _f, _vp, _vp],
                          ctypes.c_int),
     'pp_grow_connection': ([_vp, _i64, _i64, _f, _f, _f, _i32, _vp, _vp], ctypes.c_int),
+    # batched connection_value / p2p_value (csrc/edges.hip) and their host twins
+    'pp_connection_values': ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _f, _i32, _vp, _vp],
+                             ctypes.c_int),
+    'pp_p2p_values': ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _vp, _vp], ctypes.c_int),
+    'pp_connection_values_cpu': ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _f, _i32, _vp],
+                                 ctypes.c_int),
+    'pp_p2p_values_cpu': ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _vp], ctypes.c_int),
     'pp_np_exp': ([_vp, _vp, _i64, _i32, _vp], ctypes.c_int),
     'pp_np_square': ([_vp, _vp, _i64, _vp], ctypes.c_int),
     'pp_nms_workspace_size': ([_i32, _i32], _sz),

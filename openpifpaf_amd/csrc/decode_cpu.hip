@@ -38,6 +38,7 @@ struct ColSet {
     std::vector<int> by_y;   // columns with a number as source y, ascending y
     std::vector<float> ys;   // their y
     std::vector<int> nan_y;  // columns whose source y is NaN (every y test passes them)
+    bool flat = false;       // not indexed: a query visits every column (grow_connection_flat_cpu)
 
     void index(const float *r, int64_t p, int count) {
         rows = r;
@@ -98,7 +99,7 @@ void grow_connection(const ColSet &s, float x, float y, float xy_scale, bool max
             i2 = i;
         }
     };
-    if (lo_x != lo_x || hi_x != hi_x || lo_y != lo_y || hi_y != hi_y) {
+    if (s.flat || lo_x != lo_x || hi_x != hi_x || lo_y != lo_y || hi_y != hi_y) {
         for (int i = 0; i < s.n; i++) consider(i);  // NaN bounds pass every column
     } else {
         const auto b = std::lower_bound(s.ys.begin(), s.ys.end(), lo_y);
@@ -465,6 +466,18 @@ int decode_image(const float *cif, const float *caf, int K, int C, int H, int W,
 }
 
 }  // namespace
+
+// one _grow_connection over a flat (9, n) set that no decode has indexed: the host twins of
+// the batched edge values (functional_cpu.hip) score with the decoder's own function
+void pp::grow_connection_flat_cpu(const float *rows, int64_t pitch, int n, float x, float y,
+                                  float xy_scale, bool maxm, int exp_mode, float out[4]) {
+    ColSet s;
+    s.rows = rows;
+    s.pitch = pitch;
+    s.n = n;
+    s.flat = true;
+    grow_connection(s, x, y, xy_scale, maxm, exp_mode, out);
+}
 
 // `extents` (pp_decode_ragged_cpu; NULL: every image is H x W): image i is the h_i x w_i
 // top-left crop of its container planes, decoded as a batch of its own would be

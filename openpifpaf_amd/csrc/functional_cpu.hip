@@ -76,9 +76,125 @@ bool bad_field(const void *f, int64_t h, int64_t w, int64_t pitch) {
     return !f || h < 0 || w < 0 || pitch < w;
 }
 
+// ---- batched connection_value / p2p_value (cifcaf.py:194-245), edges.hip's twins ----
+inline float max0(float v) { return v > 0.0f ? v : 0.0f; }  // max(0.0, v)
+
+struct EdgeSetsCpu {
+    const float *cols;
+    const int32_t *counts;
+    int64_t set_stride, pitch;
+    int32_t n_sets;
+    const float *rows(int set) const { return cols + (int64_t)set * set_stride; }
+    int count(int set) const {  // held to [0, pitch] as the kernel holds it
+        const int64_t n = counts[set];
+        return (int)(n < 0 ? 0 : (n > pitch ? pitch : n));
+    }
+};
+
+// the admission checks of edges.hip's edge_admit, plus the queries' set indices
+int edge_admit_cpu(const char *who, const EdgeSetsCpu &s, const pp_edge_query *queries,
+                   int64_t n_q, int32_t method, const float *out, bool pairs, bool *run) {
+    *run = false;
+    if (n_q < 0 || n_q > INT32_MAX || s.n_sets < 0 || s.pitch < 0 || s.pitch > INT32_MAX ||
+        s.set_stride < 9 * s.pitch)
+        return pp::fail(PP_ESHAPE, std::string(who) + ": bad shape");
+    if (pairs && (s.n_sets & 1))
+        return pp::fail(PP_ESHAPE, std::string(who) + ": reverse_match needs the sets in "
+                                                      "(backward, forward) pairs, n_sets is odd");
+    if (method < 0 || method > 3) return pp::fail(PP_EINVAL, "connection method not known");
+    if (n_q == 0) return PP_OK;
+    if (!queries || !out || (s.n_sets > 0 && (!s.cols || !s.counts)))
+        return pp::fail(PP_EINVAL, std::string(who) + ": NULL argument");
+    for (int64_t i = 0; i < n_q; i++)
+        if (queries[i].set < 0 || queries[i].set >= s.n_sets)
+            return pp::fail(PP_EINVAL, std::string(who) + ": query " + std::to_string(i) +
+                                           " names set " + std::to_string(queries[i].set) +
+                                           " of " + std::to_string(s.n_sets));
+    *run = true;
+    return PP_OK;
+}
+
+// cifcaf.py:194-217
+void connection_value_cpu(const EdgeSetsCpu &s, const pp_edge_query &e, bool maxm, int exp_mode,
+                          float keypoint_threshold, bool reverse_match, float out[4]) {
+    const float xy_scale_s = max0(e.s);
+    float nx[4];
+    pp::grow_connection_flat_cpu(s.rows(e.set), s.pitch, s.count(e.set), e.x, e.y, xy_scale_s,
+                                 maxm, exp_mode, nx);
+    out[0] = out[1] = out[2] = out[3] = 0.0f;
+    const float ks = std::sqrt(nx[3] * e.v);  // geometric mean
+    if (ks < keypoint_threshold) return;
+    if (nx[3] == 0.0f) return;
+    if (reverse_match) {
+        float rv[4];
+        pp::grow_connection_flat_cpu(s.rows(e.set ^ 1), s.pitch, s.count(e.set ^ 1), nx[0], nx[1],
+                                     max0(nx[2]), maxm, exp_mode, rv);
+        if (rv[2] == 0.0f) return;  // tests the scale (cifcaf.py:212)
+        if (std::fabs(e.x - rv[0]) + std::fabs(e.y - rv[1]) > xy_scale_s) return;
+    }
+    out[0] = nx[0];
+    out[1] = nx[1];
+    out[2] = nx[2];
+    out[3] = ks;
+}
+
+// cifcaf.py:219-245; the running maximum is Python's max(): the first kept score, replaced
+// only by a later one that compares greater (a NaN first score stays, a later NaN never wins)
+float p2p_value_cpu(const EdgeSetsCpu &s, const pp_edge_query &e, int exp_mode) {
+    const float *r = s.rows(e.set);
+    const int64_t p = s.pitch;
+    const int n = s.count(e.set);
+    const float xy_scale_s = max0(e.s);
+    const float sbox = 2.0f * xy_scale_s;  // caf_center_s(..., sigma=2.0 * xy_scale_s)
+    const float lo_x = e.x - sbox, hi_x = e.x + sbox, lo_y = e.y - sbox, hi_y = e.y + sbox;
+    const float sigma_s2 = pp::np_pow2_f32(0.5f * xy_scale_s);
+    const float sigma_t2 = pp::np_pow2_f32(0.5f * max0(e.ts));
+    bool any = false;
+    float best = 0.0f;
+    for (int i = 0; i < n; i++) {
+        const float c1 = r[p + i], c2 = r[2 * p + i];
+        if (c1 < lo_x || c1 > hi_x || c2 < lo_y || c2 > hi_y) continue;
+        const float dx = e.x - c1, dy = e.y - c2;
+        const float ds = std::sqrt(dx * dx + dy * dy);  // np.linalg.norm(axis=0)
+        const float ex = e.tx - r[5 * p + i], ey = e.ty - r[6 * p + i];
+        const float dt = std::sqrt(ex * ex + ey * ey);
+        const float score = pp::caf_exp((-0.5f * (ds * ds)) / sigma_s2, exp_mode) *
+                            pp::caf_exp((-0.5f * (dt * dt)) / sigma_t2, exp_mode) * r[i];
+        if (!any || score > best) best = score;
+        any = true;
+    }
+    return any ? std::sqrt(e.v * best) : 0.0f;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pp_connection_values_cpu(const float *cols, int64_t set_stride, int64_t pitch,
+                             const int32_t *counts, int32_t n_sets, const pp_edge_query *queries,
+                             int64_t n_q, int32_t method, float keypoint_threshold,
+                             int32_t reverse_match, float *out) {
+    const EdgeSetsCpu s{cols, counts, set_stride, pitch, n_sets};
+    bool run;
+    const int rc = edge_admit_cpu("pp_connection_values_cpu", s, queries, n_q, method, out,
+                                  reverse_match != 0, &run);
+    if (rc != PP_OK || !run) return rc;
+    for (int64_t i = 0; i < n_q; i++)
+        connection_value_cpu(s, queries[i], (method & 1) != 0, (method >> 1) & 1,
+                             keypoint_threshold, reverse_match != 0, out + 4 * i);
+    return PP_OK;
+}
+
+int pp_p2p_values_cpu(const float *cols, int64_t set_stride, int64_t pitch, const int32_t *counts,
+                      int32_t n_sets, const pp_edge_query *queries, int64_t n_q, int32_t method,
+                      float *out) {
+    const EdgeSetsCpu s{cols, counts, set_stride, pitch, n_sets};
+    bool run;
+    const int rc = edge_admit_cpu("pp_p2p_values_cpu", s, queries, n_q, method, out, false, &run);
+    if (rc != PP_OK || !run) return rc;
+    for (int64_t i = 0; i < n_q; i++) out[i] = p2p_value_cpu(s, queries[i], (method >> 1) & 1);
+    return PP_OK;
+}
 
 int pp_scalar_square_add_gauss_with_max_cpu(float *field, int64_t h, int64_t w, int64_t pitch,
                                             const float *x, const float *y, const float *sigma,

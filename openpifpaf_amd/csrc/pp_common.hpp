@@ -23,6 +23,10 @@ void set_error(const std::string &msg);
 // Annotation.score() of a host record (stages_cpu.hip): zero_j >= 0 suppress_score_index,
 // w the record's own score_weights (NULL: the default weights)
 double ann_score_cpu(const pp_ann &a, int K, int zero_j = -1, const double *w = nullptr);
+// _grow_connection + blend / max (cifcaf.py:124-192) on the host over a flat (9, n) column
+// set with row pitch `pitch` (decode_cpu.hip's grow_connection, every column visited)
+void grow_connection_flat_cpu(const float *rows, int64_t pitch, int n, float x, float y,
+                              float xy_scale, bool maxm, int exp_mode, float out[4]);
 int fail(int status, const std::string &msg);
 int check_launch(const char *what);
 

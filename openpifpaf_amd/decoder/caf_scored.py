@@ -7,6 +7,7 @@ import torch
 
 from .. import _device
 from .._abi import make_config, scale_list, skeleton_array
+from .._edges import PackedSets
 from .._lib import call
 from ._fields import batch1, head_scales, pitched_hr, with_geometry
 from .field_config import FieldConfig
@@ -23,6 +24,7 @@ class CafScored:
         self.cif_floor = cif_floor
         self.forward = None
         self.backward = None
+        self.packed = None
 
     def directed(self, caf_i, forward):
         if forward:
@@ -59,7 +61,12 @@ class CafScored:
             bwd = [np.ascontiguousarray(a) for a in bwd]
         if self.forward is None:
             self.forward, self.backward = fwd, bwd
+            # the device buffer of a single fill, as CifCaf.connection_values / p2p_values
+            # read it (set 2 caf_i backward, 2 caf_i + 1 forward); the lists are views of it
+            self.packed = None if host else PackedSets(
+                cols[0].view(2 * n_caf, 9, max(1, cap)), counts[0].view(2 * n_caf))
         else:
+            self.packed = None  # concatenated columns are repacked
             cat = (lambda a, b: np.concatenate((a, np.asarray(b)), axis=1)) if host else \
                 (lambda a, b: torch.cat((_device.to_device(a), b), dim=1))
             self.forward = [cat(a, b) for a, b in zip(self.forward, fwd)]

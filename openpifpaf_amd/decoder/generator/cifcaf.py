@@ -8,17 +8,18 @@ Annotation objects.  `decode_batch` decodes a whole (B, ...) batch of device fie
 one launch sequence, which is how `batch()` (generator.py:84-101) is served.
 """
 from collections import defaultdict
+import ctypes
 import logging
 import time
 
 import numpy as np
 
-from ... import _device
+from ... import _device, _edges, functional
 from ..._abi import PACK_ALL, check_seed_mask, make_config, skeleton_array
 from ...annotation import Annotation
 from ...distributed import decode_sharded, shard
 from ...engine import HeadSet, InitialAnnotations, RaggedFields, engine
-from ...functional import grow_connection_blend
+from ...functional import _edge_call, grow_connection_blend
 from .. import nms as nms_module
 from ..caf_scored import CafScored
 from ..cif_hr import CifHr
@@ -347,3 +348,67 @@ class CifCaf(Generator):
         assert caf_field.shape[0] == 9
         return grow_connection_blend(caf_field, xy[0], xy[1], xy_scale,
                                      connection_method=self.connection_method)
+
+    def connection_value(self, ann, caf_scored, start_i, end_i, *, reverse_match=True):
+        """cifcaf.py:194-217 on the device (one launch of pp_connection_values): the joint
+        that the CAF from start_i to end_i connects ann's start joint to, as (x, y, scale,
+        score) of four np.float32, or (0.0, 0.0, 0.0, 0.0).  caf_scored: anything with the
+        reference's directed(caf_i, forward), host- or device-backed.  Inputs are converted
+        to float32 first: for Python-float inputs the reference computes (and returns) in
+        float64, which this does not follow."""
+        caf_i, forward = self.by_source[start_i][end_i]
+        caf_f, caf_b = caf_scored.directed(caf_i, forward)
+        xyv = ann.data[start_i]
+        r = functional.connection_values(
+            [caf_b, caf_f], [[xyv[0], xyv[1], xyv[2], ann.joint_scales[start_i]]], [1],
+            connection_method=self.connection_method,
+            keypoint_threshold=self.keypoint_threshold, reverse_match=reverse_match)[0]
+        if not r.any():
+            return 0.0, 0.0, 0.0, 0.0
+        return tuple(np.float32(v) for v in r)
+
+    @staticmethod
+    def p2p_value(source_xyv, caf_scored, source_s, target_xysv, caf_i, forward):
+        """cifcaf.py:219-245 on the device (one launch of pp_p2p_values): how well the CAF
+        caf_i connects the source joint to the target joint, an np.float32, or 0.0 when no
+        column lies in the source's box.  The reference's max() over the kept columns is
+        restated: NaN exactly when the first kept column's score is NaN, a NaN of a later
+        column is ignored.  Inputs are converted to float32 first (the reference computes
+        Python-float inputs in float64; this does not)."""
+        caf_f, _ = caf_scored.directed(caf_i, forward)
+        r = functional.p2p_values(
+            [caf_f], [[source_xyv[0], source_xyv[1], source_xyv[2], source_s]],
+            [[target_xysv[0], target_xysv[1], target_xysv[2]]], [0])[0]
+        return 0.0 if r.view(np.uint32) == 0 else np.float32(r)
+
+    def connection_values(self, anns, caf_scored, *, reverse_match=True, device=False):
+        """connection_value for every directed skeleton edge of every annotation in ONE
+        launch: (n_ann, 2C, 4) float32, [a, 2 * caf_i] the forward edge (start j1, end j2)
+        and [a, 2 * caf_i + 1] the backward one (start j2, end j1) of self.skeleton's CAF
+        caf_i.  Each element is what connection_value returns for that argument tuple,
+        unset start joints (v == 0) included.  device=True: a device tensor, no sync."""
+        q = _edges.connection_queries(_edges.annotation_table(anns, len(self.keypoints)),
+                                      self.skeleton_m1)
+        sets = _edges.caf_scored_sets(caf_scored, len(self.skeleton_m1), _device.require())
+        r = _edge_call('pp_connection_values', sets, q,
+                       _edges.method_bits(self.connection_method, 'numpy_simd'),
+                       (ctypes.c_float(self.keypoint_threshold),
+                        ctypes.c_int32(bool(reverse_match))), (4,), device)
+        return r.reshape(len(anns), 2 * len(self.skeleton_m1), 4)
+
+    @staticmethod
+    def p2p_values(sources, targets, caf_scored, skeleton, *, device=False):
+        """p2p_value of every source annotation's joint at an edge's start against every
+        target annotation's joint at its end, in ONE launch: (n_src, n_tgt, C, 2) float32,
+        [s, t, caf_i, 0] forward (source joint j1, target joint j2), [s, t, caf_i, 1]
+        backward (source j2, target j1).  skeleton: 1-based joint pairs, as CifCaf's.  Each
+        element is what p2p_value returns for that argument tuple, unset joints included.
+        device=True: a device tensor, no sync."""
+        skel = np.asarray(skeleton, dtype=np.int64).reshape(-1, 2) - 1
+        k = int(skel.max()) + 1 if len(skel) else 0
+        q = _edges.p2p_queries(_edges.annotation_table(sources, k),
+                               _edges.annotation_table(targets, k), skel)
+        sets = _edges.caf_scored_sets(caf_scored, len(skel), _device.require())
+        r = _edge_call('pp_p2p_values', sets, q, _edges.method_bits('blend', 'numpy_simd'), (),
+                       (), device)
+        return r.reshape(len(sources), len(targets), len(skel), 2)

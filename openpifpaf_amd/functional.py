@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _device
+from . import _device, _edges
 from ._abi import EXP_MODES
 from ._lib import call
 
@@ -286,3 +286,54 @@ def grow_connection_blend(caf_field, x, y, xy_scale, connection_method='blend',
 
 
 __all__.append('grow_connection_blend')
+
+
+def _edge_call(name, sets, q, method, extra, width, device):
+    """One launch of pp_connection_values / pp_p2p_values; the result stays on the device
+    (no synchronisation) with `device`, else comes back as a NumPy array."""
+    dev = _device.require()
+    packed = _edges.pack_sets(sets, dev)
+    _edges.check_sets(q, packed.n_sets)
+    n_q = len(q)
+    qd = torch.from_numpy(np.ascontiguousarray(q).view(np.uint8)).to(dev)
+    out = torch.empty((n_q,) + width, dtype=torch.float32, device=dev)
+    cols = packed.cols if packed.cols.is_contiguous() else packed.cols.contiguous()
+    call(name, _device.ptr(cols), ctypes.c_int64(9 * packed.cap), ctypes.c_int64(packed.cap),
+         _device.ptr(packed.counts), ctypes.c_int32(packed.n_sets), _device.ptr(qd),
+         ctypes.c_int64(n_q), ctypes.c_int32(method), *extra, _device.ptr(out), _device.stream())
+    return out if device else out.cpu().numpy()
+
+
+def connection_values(sets, sources, set_index, *, connection_method='blend',
+                      exp_mode='numpy_simd', keypoint_threshold=0.0, reverse_match=True,
+                      device=False):
+    """CifCaf.connection_value (cifcaf.py:194-217) for a batch of queries in ONE launch
+    (pp_connection_values), next to grow_connection_blend's one launch per query.
+
+    sets: a list of (9, N) column sets (NumPy or device), or an _edges.PackedSets; in
+    (backward, forward) pairs, so that the reverse match of a query on set s reads set s ^ 1
+    (with reverse_match their number must be even).  sources: (n, 4) = (x, y, v, scale) of
+    each start joint; set_index: (n) the set each query grows over (caf_f).  Inputs are
+    converted to float32 first (the reference computes Python-float inputs in float64; this
+    does not).  Returns (n, 4) float32 (x, y, scale, score), rows of zeros where the
+    reference returns (0.0, 0.0, 0.0, 0.0); device=True: a device tensor, no sync."""
+    q = _edges.queries(sources, set_index)
+    return _edge_call('pp_connection_values', sets, q,
+                      _edges.method_bits(connection_method, exp_mode),
+                      (ctypes.c_float(keypoint_threshold), ctypes.c_int32(bool(reverse_match))),
+                      (4,), device)
+
+
+def p2p_values(sets, sources, targets, set_index, *, exp_mode='numpy_simd', device=False):
+    """CifCaf.p2p_value (cifcaf.py:219-245) for a batch of queries in one launch
+    (pp_p2p_values).  sets, sources, set_index as connection_values; targets: (n, 3) =
+    (x, y, scale) of each target joint.  Returns (n) float32, 0.0 where no column lies in
+    the source's box.  Python's max() over the kept columns (cifcaf.py:245) is restated as:
+    NaN exactly when the first kept column's score is NaN, later NaN scores ignored.  Inputs
+    are converted to float32 first."""
+    q = _edges.queries(sources, set_index, targets)
+    return _edge_call('pp_p2p_values', sets, q, _edges.method_bits('blend', exp_mode), (), (),
+                      device)
+
+
+__all__ += ['connection_values', 'p2p_values']

@@ -6,12 +6,14 @@ Same names, signatures, defaults, return types and ValueError messages as
 `openpifpaf_amd.functional` (the device API) and the reference's Cython module.  This is an
 explicit choice of the caller: `openpifpaf_amd.functional` and the decoder never fall back
 to it, and it raises, like every other entry point, when the library is missing.
-(grow_connection_blend is decoder-internal, cifcaf.py:124-192, and stays device-only.)
+(grow_connection_blend is decoder-internal, cifcaf.py:124-192, and stays device-only; the
+batched connection_values / p2p_values, cifcaf.py:194-245, have their host twins here.)
 """
 import ctypes
 
 import numpy as np
 
+from . import _edges
 from ._lib import call
 from .functional import _buf
 
@@ -202,3 +204,37 @@ __all__ = [
     'scalar_nonzero', 'scalar_nonzero_clipped', 'scalar_nonzero_clipped_with_reduction',
     'paf_center_b', 'paf_center', 'caf_center_s', 'occupancy_set',
 ]
+
+
+def _edge_call(name, sets, q, method, extra, width):
+    packed = _edges.pack_sets(sets)
+    _edges.check_sets(q, packed.n_sets)
+    cols = np.ascontiguousarray(packed.cols, np.float32)
+    counts = np.ascontiguousarray(packed.counts, np.int32)
+    q = np.ascontiguousarray(q)
+    out = np.zeros((len(q),) + width, np.float32)
+    call(name, cols.ctypes.data, ctypes.c_int64(9 * packed.cap), ctypes.c_int64(packed.cap),
+         counts.ctypes.data, ctypes.c_int32(packed.n_sets), q.ctypes.data,
+         ctypes.c_int64(len(q)), ctypes.c_int32(method), *extra, out.ctypes.data)
+    return out
+
+
+def connection_values(sets, sources, set_index, *, connection_method='blend',
+                      exp_mode='numpy_simd', keypoint_threshold=0.0, reverse_match=True):
+    """functional.connection_values on the host (pp_connection_values_cpu): CifCaf.
+    connection_value (cifcaf.py:194-217) per query, byte-identical with the kernel."""
+    q = _edges.queries(sources, set_index)
+    return _edge_call('pp_connection_values_cpu', sets, q,
+                      _edges.method_bits(connection_method, exp_mode),
+                      (ctypes.c_float(keypoint_threshold), ctypes.c_int32(bool(reverse_match))),
+                      (4,))
+
+
+def p2p_values(sets, sources, targets, set_index, *, exp_mode='numpy_simd'):
+    """functional.p2p_values on the host (pp_p2p_values_cpu): CifCaf.p2p_value
+    (cifcaf.py:219-245) per query, byte-identical with the kernel."""
+    q = _edges.queries(sources, set_index, targets)
+    return _edge_call('pp_p2p_values_cpu', sets, q, _edges.method_bits('blend', exp_mode), (), ())
+
+
+__all__ += ['connection_values', 'p2p_values']
