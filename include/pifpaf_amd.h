@@ -608,6 +608,35 @@ int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
                                void *stream);
 
 /*
+ * pp_fields_from_conv_ragged for channels-last (NHWC) conv outputs and their slices, read where
+ * they lie: the interleaved class of pp_fields_from_conv_strided, per image.  Inside image i's
+ * own field every value is, bit for bit, what pp_fields_from_conv_ex gives for the dense
+ * (1, channels, h_i, w_i) copy of that image alone with the same conv_dtype, mirror, src_field
+ * and swap_ends (the mirror is about the image's own W_i); outside it the value is +0; every
+ * element of the written fields is stored exactly once.  The container's bytes are those of
+ * pp_fields_from_conv_ragged on the NCHW copies of the same values.  The arguments are those
+ * of pp_fields_from_conv_ragged but for
+ *   conv_strides  HOST (n_img, 2) or NULL: each image's ROW and COLUMN strides in elements;
+ *                 the channel stride is 1.  NULL = every image dense channels-last (column
+ *                 stride channels, row stride w_i * channels).  The stride of a dimension of
+ *                 extent 1 is ignored.  A channel slice of a wider channels-last tensor is
+ *                 such a view; its channel runs may start at any element offset.
+ * d_tables has the size and layout of pp_fields_from_conv_ragged's (pp_ragged_conv_tables_size,
+ * the field extent table at pp_ragged_conv_extents_offset) and is staged in the same way:
+ * pageable host tables are consumed before the call returns, pinned ones when the stream
+ * reaches the copy.  A workgroup reads the channel runs of 16 conv pixels of one row with
+ * 16-byte loads and transposes them in LDS; the tiles cover the container.  The checks, their
+ * codes and their order are those of pp_fields_from_conv_ragged, with more than 65535 channel
+ * chunks (channels / 512 at quad <= 1) -> PP_ESHAPE beside the other grid limits; n_img = 0
+ * returns PP_OK after the checks.  No device memory is allocated.  Offsets are 64-bit.
+ */
+int pp_fields_from_conv_ragged_interleaved(const void *const *convs, int32_t conv_dtype,
+        const int32_t *conv_extents, const int64_t *conv_strides, int32_t n_img, int32_t n_fields,
+        int32_t layout, int32_t quad, int32_t mirror, const int32_t *src_field,
+        const uint8_t *swap_ends, int32_t H, int32_t W, float *d_container, int32_t out_fields,
+        int32_t out_field0, void *d_tables, size_t tables_bytes, void *stream);
+
+/*
  * nms.Keypoints.annotations (nms.py:17-57) over caller records, n_img independent groups:
  * d_anns (n_img, ann_capacity) with d_counts[i] records in group i (modified in place as
  * the reference modifies its Annotation objects: joints below keypoint_threshold zeroed,

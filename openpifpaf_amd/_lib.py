@@ -126,6 +126,10 @@ _SIGNATURES = {
     'pp_ragged_conv_extents_offset': ([_i32], _sz),
     'pp_fields_from_conv_ragged': ([_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                     _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp], ctypes.c_int),
+    # ... from channels-last conv outputs, read in place
+    'pp_fields_from_conv_ragged_interleaved': ([_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+                                                _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz,
+                                                _vp], ctypes.c_int),
     'pp_nms_keypoints': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
                          ctypes.c_int),
     'pp_nms_keypoints_scored': ([_vp, _vp, _i32, _i32, _i32, _vp, _f64, _vp, _vp, _vp, _vp,

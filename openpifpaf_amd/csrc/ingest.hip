@@ -22,6 +22,10 @@
 // (channels-last and its slices) goes through ingest_interleaved_kernel: a workgroup loads
 // the channel runs of 16 conv pixels of one row, lanes along the channels, transposes them
 // in LDS and writes with lanes along X, as the planar kernel does.
+//
+// pp_fields_from_conv_ragged and pp_fields_from_conv_ragged_interleaved write the conv outputs
+// of n images of their own sizes into one container, the first from planar views
+// (ingest_ragged_kernel), the second from channels-last ones (ingest_ragged_interleaved_kernel).
 #include <hip/hip_fp16.h>
 
 #include "pp_common.hpp"
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256) void ingest_strided_kernel(IngestArgs a, Inges
 // and its conv extents.  field_ext is written here, the (H_i, W_i) pp_decode_ragged reads.
 struct IngestRagged {
     const void *const *conv;  // (n)
-    const int64_t *strides;   // (n, 2) channel, row; or NULL
+    const int64_t *strides;   // (n, 2) channel, row (interleaved kernel: row, column); or NULL
     const int32_t *conv_ext;  // (n, 2) h_i, w_i
     int32_t *field_ext;       // (n, 2) H_i, W_i
 };
@@ -252,6 +256,49 @@ __device__ __forceinline__ void spill_vec(const T *tag, uint4 v, float *row) {
     }
 }
 
+// The load phase of the two interleaved kernels, as text for the reason PP_INGEST_PIXEL is
+// (the instances of ingest_interleaved_kernel compile to the code they had with these lines
+// written out).  One wave per pixel, lanes along its channel run; 16-byte loads between the
+// run's first and last 16-byte boundary, single elements before and after (a slice at an odd
+// channel offset is aligned to its element only).  All of a wave's loads are issued before its
+// first LDS write, so that they are in flight together: kPix pixels, each at most kIter
+// vectors and two elements a lane.  RUN is the address of conv channel 0 of the chunk at
+// pixel p of the tile; T, kVec, lane, wave, n (conv channels of the chunk), n_pix (pixels of
+// the tile to load: none past it is touched), g and lds are the kernel's.
+#define PP_INGEST_TILE_LOAD(RUN)                                                              \
+    constexpr int kPix = kTilePix / 4, kIter = kMaxChunkCh / kVec / 64;                       \
+    const T *run[kPix];                                                                       \
+    int head[kPix], n_vec[kPix];                                                              \
+    uint4 vec[kPix][kIter];                                                                   \
+    float first[kPix], last[kPix];                                                            \
+    _Pragma("unroll") for (int i = 0; i < kPix; i++) {                                        \
+        const int p = wave + 4 * i;                                                           \
+        n_vec[i] = head[i] = 0;                                                               \
+        if (p >= n_pix) continue;                                                             \
+        run[i] = RUN;                                                                         \
+        const int to_boundary = (int)((16 - ((uintptr_t)run[i] & 15)) & 15) / (int)sizeof(T); \
+        head[i] = min(to_boundary, n);                                                        \
+        n_vec[i] = (n - head[i]) / kVec;                                                      \
+        if (lane < head[i]) first[i] = load_f32(run[i] + lane);                               \
+        _Pragma("unroll") for (int j = 0; j < kIter; j++)                                     \
+            if (lane + 64 * j < n_vec[i])                                                     \
+                vec[i][j] = *reinterpret_cast<const uint4 *>(run[i] + head[i] +               \
+                                                             (lane + 64 * j) * kVec);         \
+        const int c = head[i] + n_vec[i] * kVec + lane;                                       \
+        if (c < n) last[i] = load_f32(run[i] + c);                                            \
+    }                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < kPix; i++) {                                        \
+        const int p = wave + 4 * i;                                                           \
+        if (p >= n_pix) continue;                                                             \
+        float *row = lds + p * g.lds_pitch;                                                   \
+        if (lane < head[i]) row[lane] = first[i];                                             \
+        _Pragma("unroll") for (int j = 0; j < kIter; j++)                                     \
+            if (lane + 64 * j < n_vec[i])                                                     \
+                spill_vec(run[i], vec[i][j], row + head[i] + (lane + 64 * j) * kVec);         \
+        const int c = head[i] + n_vec[i] * kVec + lane;                                       \
+        if (c < n) row[c] = last[i];                                                          \
+    }
+
 template <typename T, bool kEx>
 __global__ __launch_bounds__(256) void ingest_interleaved_kernel(IngestArgs a, IngestFlip t,
                                                                  IngestStrides s, IngestTile g) {
@@ -267,48 +314,9 @@ __global__ __launch_bounds__(256) void ingest_interleaved_kernel(IngestArgs a, I
     const int n = (cb1 - cb0) << shift;  // conv channels of the chunk
     const int n_pix = min(kTilePix, a.w - x0t);
 
-    // load: one wave per pixel, lanes along its channel run; 16-byte loads between the
-    // run's first and last 16-byte boundary, single elements before and after (a slice at
-    // an odd channel offset is aligned to its element only).  All of a wave's loads are
-    // issued before its first LDS write, so that they are in flight together: kPix pixels,
-    // each at most kIter vectors and two elements a lane.
-    constexpr int kPix = kTilePix / 4, kIter = kMaxChunkCh / kVec / 64;
-    const T *run[kPix];
-    int head[kPix], n_vec[kPix];
-    uint4 vec[kPix][kIter];
-    float first[kPix], last[kPix];
-#pragma unroll
-    for (int i = 0; i < kPix; i++) {
-        const int p = wave + 4 * i;
-        n_vec[i] = head[i] = 0;
-        if (p >= n_pix) continue;
-        run[i] = (const T *)a.conv + (int64_t)img * s.img + (int64_t)y0 * s.row +
-                 (int64_t)(x0t + p) * s.col + ((int64_t)cb0 << shift);
-        const int to_boundary = (int)((16 - ((uintptr_t)run[i] & 15)) & 15) / (int)sizeof(T);
-        head[i] = min(to_boundary, n);
-        n_vec[i] = (n - head[i]) / kVec;
-        if (lane < head[i]) first[i] = load_f32(run[i] + lane);
-#pragma unroll
-        for (int j = 0; j < kIter; j++)
-            if (lane + 64 * j < n_vec[i])
-                vec[i][j] = *reinterpret_cast<const uint4 *>(run[i] + head[i] +
-                                                             (lane + 64 * j) * kVec);
-        const int c = head[i] + n_vec[i] * kVec + lane;
-        if (c < n) last[i] = load_f32(run[i] + c);
-    }
-#pragma unroll
-    for (int i = 0; i < kPix; i++) {
-        const int p = wave + 4 * i;
-        if (p >= n_pix) continue;
-        float *row = lds + p * g.lds_pitch;
-        if (lane < head[i]) row[lane] = first[i];
-#pragma unroll
-        for (int j = 0; j < kIter; j++)
-            if (lane + 64 * j < n_vec[i])
-                spill_vec(run[i], vec[i][j], row + head[i] + (lane + 64 * j) * kVec);
-        const int c = head[i] + n_vec[i] * kVec + lane;
-        if (c < n) row[c] = last[i];
-    }
+    // load: one wave per pixel, lanes along its channel run (PP_INGEST_TILE_LOAD above)
+    PP_INGEST_TILE_LOAD((const T *)a.conv + (int64_t)img * s.img + (int64_t)y0 * s.row +
+                        (int64_t)(x0t + p) * s.col + ((int64_t)cb0 << shift))
     __syncthreads();
 
     // store: lanes along X, then the tile's output rows, then the fields
@@ -351,6 +359,93 @@ __global__ __launch_bounds__(256) void ingest_interleaved_kernel(IngestArgs a, I
     }
 }
 
+// ingest_interleaved_kernel's tile over the CONTAINER (pp_fields_from_conv_ragged_interleaved):
+// blockIdx.x counts (conv row, 16-pixel tile) of ceil(a.H / 2^quad) rows of g.tiles_x tiles,
+// which own every container pixel; r.strides holds each image's ROW and COLUMN strides (NULL:
+// dense channels-last), the channel stride is 1.  A tile loads the pixels inside the image's
+// conv extent only (one wholly outside loads nothing) and stores, for the output channels of
+// its chunk, the ingested value inside the image's own field, mirrored about the image's own
+// width, and +0 outside it at the unmirrored position: every element of the written fields
+// is stored exactly once.  The image is blockIdx.z, so its table entries are scalar loads.
+template <typename T, bool kEx>
+__global__ __launch_bounds__(256) void ingest_ragged_interleaved_kernel(IngestArgs a, IngestFlip t,
+                                                                        IngestRagged r,
+                                                                        IngestTile g) {
+    __shared__ float lds[kLdsFloats];
+    constexpr int kVec = 16 / (int)sizeof(T);  // elements per 16-byte load
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int img = blockIdx.z;
+    const int h = r.conv_ext[2 * img], w = r.conv_ext[2 * img + 1];
+    int Hi = h, Wi = w;
+    for (int q = 0; q < a.quad; q++) {  // pp_fields_dim
+        Hi = 2 * Hi - 1;
+        Wi = 2 * Wi - 1;
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+        r.field_ext[2 * img] = Hi;
+        r.field_ext[2 * img + 1] = Wi;
+    }
+    const int y0 = blockIdx.x / g.tiles_x, x0t = (blockIdx.x % g.tiles_x) * kTilePix;
+    const int shift = 2 * a.quad;
+    const int cb0 = blockIdx.y * g.chunk_base;  // first pre-dequad channel of the chunk
+    const int n_base = (int)(a.conv_ch >> shift);
+    const int cb1 = min(cb0 + g.chunk_base, n_base);
+    const int n = (cb1 - cb0) << shift;  // conv channels of the chunk
+    const int n_pix = y0 < h ? min(kTilePix, w - x0t) : 0;  // <= 0: the tile is outside the image
+
+    // a stride whose extent is 1 meets index 0 only
+    const int64_t s_row = h == 1 ? 0 : r.strides ? r.strides[2 * img] : (int64_t)w * a.conv_ch;
+    const int64_t s_col = w == 1 ? 0 : r.strides ? r.strides[2 * img + 1] : a.conv_ch;
+    const T *row0 = (const T *)r.conv[img] + (int64_t)y0 * s_row + ((int64_t)cb0 << shift);
+    PP_INGEST_TILE_LOAD(row0 + (int64_t)(x0t + p) * s_col)
+    __syncthreads();
+
+    // store: lanes along X, then the tile's output rows, then the fields
+    const int64_t HW = (int64_t)a.H * a.W;
+    const bool mirror = kEx && t.mirror != 0;
+    const int x_bits = 4 + a.quad;  // kTilePix << quad output columns
+    static_assert(kTilePix == 16, "x_bits assumes 16 pixels per tile");
+    const int n_work = a.n_fields << (x_bits + a.quad);
+    for (int e = tid; e < n_work; e += 256) {
+        const int xl = e & ((1 << x_bits) - 1);
+        const int yr = (e >> x_bits) & ((1 << a.quad) - 1);
+        const int f = e >> (x_bits + a.quad);
+        const int xs = (x0t << a.quad) + xl;  // source column after the dequads
+        const int Y = (y0 << a.quad) + yr;
+        if (xs >= a.W || Y >= a.H) continue;  // outside the container
+        // inside the image's own field (the crop is against it) the conv pixel is in the
+        // LDS image: xs < Wi = 2^quad (w - 1) + 1 gives xs >> quad < w, and Y likewise
+        const bool inside = xs < Wi && Y < Hi;
+        const int X = inside && mirror ? Wi - 1 - xs : xs;
+        int fs = f;
+        bool swap = false;
+        if (kEx) {
+            if (t.has_src) fs = t.src_field[f];
+            swap = f < kMaxTableFields && ((t.swap_mask >> f) & 1);
+        }
+        int sub = 0, yy = Y, xx = xs;
+        for (int q = 0; q < a.quad; q++) {
+            sub = 4 * sub + (2 * (yy & 1) + (xx & 1));
+            yy >>= 1;
+            xx >>= 1;
+        }
+        const float *src = lds + (xl >> a.quad) * g.lds_pitch + sub;
+        float *dst = a.out + (((int64_t)img * a.out_fields + a.out_field0 + f) * a.n_out) * HW +
+                     (int64_t)Y * a.W + X;
+        for (int o = 0; o < a.n_out; o++) {
+            const int op = a.op[o];
+            int comp = a.comp[o];
+            if (kEx && swap && (op == 3 || op == 4)) comp ^= 2;
+            const int cb = a.grp_off[o] + fs * a.fld_mul[o] + comp;
+            if (cb < cb0 || cb >= cb1) continue;  // another chunk's workgroup writes it, zeros too
+            dst[(int64_t)o * HW] =
+                inside ? ingest_value(op, src[(cb - cb0) << shift], mirror, X, Y) : 0.0f;
+        }
+    }
+}
+
+#undef PP_INGEST_TILE_LOAD
+
 enum Route { kDense, kPlanar, kInterleaved };
 
 template <typename T>
@@ -385,6 +480,20 @@ static void launch_ingest_ragged(const IngestArgs &a, const IngestFlip &t, const
         hipLaunchKernelGGL((ingest_ragged_kernel<T, true>), grid, dim3(256), 0, stream, a, t, r);
     else
         hipLaunchKernelGGL((ingest_ragged_kernel<T, false>), grid, dim3(256), 0, stream, a, t, r);
+}
+
+template <typename T>
+static void launch_ingest_ragged_interleaved(const IngestArgs &a, const IngestFlip &t,
+                                             const IngestRagged &r, const IngestTile &g,
+                                             int n_chunks, bool ex, hipStream_t stream) {
+    const int rows = (a.H + (1 << a.quad) - 1) >> a.quad;
+    const dim3 tiles((unsigned)(rows * g.tiles_x), (unsigned)n_chunks, (unsigned)a.n_img);
+    if (ex)
+        hipLaunchKernelGGL((ingest_ragged_interleaved_kernel<T, true>), tiles, dim3(256), 0,
+                           stream, a, t, r, g);
+    else
+        hipLaunchKernelGGL((ingest_ragged_interleaved_kernel<T, false>), tiles, dim3(256), 0,
+                           stream, a, t, r, g);
 }
 
 }  // namespace pp
@@ -585,14 +694,17 @@ size_t pp_ragged_conv_extents_offset(int32_t n_img) {
                      : 0;
 }
 
-int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
-                               const int32_t *conv_extents, const int64_t *conv_strides,
-                               int32_t n_img, int32_t n_fields, int32_t layout, int32_t quad,
-                               int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
-                               int32_t H, int32_t W, float *d_container, int32_t out_fields,
-                               int32_t out_field0, void *d_tables, size_t tables_bytes,
-                               void *stream) {
-    const std::string name("pp_fields_from_conv_ragged");
+// The two ragged symbols: conv_strides holds (channel, row) with column stride 1 for the planar
+// one, (row, column) with channel stride 1 for the interleaved one.
+static int fields_from_conv_ragged(const char *who, bool interleaved, const void *const *convs,
+                                   int32_t conv_dtype, const int32_t *conv_extents,
+                                   const int64_t *conv_strides, int32_t n_img, int32_t n_fields,
+                                   int32_t layout, int32_t quad, int32_t mirror,
+                                   const int32_t *src_field, const uint8_t *swap_ends, int32_t H,
+                                   int32_t W, float *d_container, int32_t out_fields,
+                                   int32_t out_field0, void *d_tables, size_t tables_bytes,
+                                   void *stream) {
+    const std::string name(who);
     if (!convs || !conv_extents || !d_container || !d_tables)
         return fail(PP_EINVAL, name + ": NULL argument");
     if (n_img < 0 || n_fields <= 0 || H <= 0 || W <= 0 || quad < 0 || quad > 4)
@@ -607,6 +719,21 @@ int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
         return fail(PP_ESHAPE, name + ": bad shape (a product beyond int32)");
     if (n_img > 65535 || n_fields > 65535)
         return fail(PP_ESHAPE, name + ": more than 65535 images or fields (the launch grid)");
+    IngestTile g{};
+    int n_chunks = 1;
+    if (interleaved) {
+        // chunks of whole pre-dequad channels, as even as the LDS image allows; the tiles
+        // cover the container (rows * tiles_x <= H * W, which is inside int32)
+        const int n_base = (int)(a.conv_ch >> (2 * quad));
+        const int most = kMaxChunkCh >> (2 * quad);  // >= 2: quad <= 4
+        n_chunks = (n_base + most - 1) / most;
+        if (n_chunks > 65535)
+            return fail(PP_ESHAPE, name + ": more than 65535 channel chunks (the launch grid)");
+        g.tiles_x = (((W + (1 << quad) - 1) >> quad) + kTilePix - 1) / kTilePix;
+        g.chunk_base = (n_base + n_chunks - 1) / n_chunks;
+        const int ch = g.chunk_base << (2 * quad);
+        g.lds_pitch = ch + ((2 - ch) & 31);
+    }
     const uintptr_t elem = conv_dtype == PP_DTYPE_F32 ? 4 : 2;
     for (int i = 0; i < n_img; i++) {
         if (!convs[i]) return fail(PP_EINVAL, name + ": NULL conv pointer");
@@ -617,7 +744,11 @@ int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
         if (pp_fields_dim(h, quad) > H || pp_fields_dim(w, quad) > W)
             return fail(PP_ESHAPE, name + ": field extent outside the container");
         // the stride of a dimension of extent 1 says nothing (the channels are never 1)
-        if (conv_strides && (conv_strides[2 * i] < 0 || (h > 1 && conv_strides[2 * i + 1] < 0)))
+        if (conv_strides && !interleaved &&
+            (conv_strides[2 * i] < 0 || (h > 1 && conv_strides[2 * i + 1] < 0)))
+            return fail(PP_EINVAL, name + ": negative conv stride");
+        if (conv_strides && interleaved &&
+            ((h > 1 && conv_strides[2 * i] < 0) || (w > 1 && conv_strides[2 * i + 1] < 0)))
             return fail(PP_EINVAL, name + ": negative conv stride");
     }
     if (n_img == 0) return PP_OK;
@@ -652,13 +783,44 @@ int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
     r.conv_ext = (const int32_t *)(tab + cext_off);
     r.field_ext = (int32_t *)(tab + pp_ragged_conv_extents_offset(n_img));
     const bool ex = t.mirror || t.has_src || t.swap_mask;
-    if (conv_dtype == PP_DTYPE_F32)
+    if (interleaved && conv_dtype == PP_DTYPE_F32)
+        launch_ingest_ragged_interleaved<float>(a, t, r, g, n_chunks, ex, s);
+    else if (interleaved && conv_dtype == PP_DTYPE_F16)
+        launch_ingest_ragged_interleaved<__half>(a, t, r, g, n_chunks, ex, s);
+    else if (interleaved)
+        launch_ingest_ragged_interleaved<Bf16>(a, t, r, g, n_chunks, ex, s);
+    else if (conv_dtype == PP_DTYPE_F32)
         launch_ingest_ragged<float>(a, t, r, ex, s);
     else if (conv_dtype == PP_DTYPE_F16)
         launch_ingest_ragged<__half>(a, t, r, ex, s);
     else
         launch_ingest_ragged<Bf16>(a, t, r, ex, s);
-    return check_launch("pp_fields_from_conv_ragged");
+    return check_launch(who);
+}
+
+int pp_fields_from_conv_ragged(const void *const *convs, int32_t conv_dtype,
+                               const int32_t *conv_extents, const int64_t *conv_strides,
+                               int32_t n_img, int32_t n_fields, int32_t layout, int32_t quad,
+                               int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends,
+                               int32_t H, int32_t W, float *d_container, int32_t out_fields,
+                               int32_t out_field0, void *d_tables, size_t tables_bytes,
+                               void *stream) {
+    return fields_from_conv_ragged("pp_fields_from_conv_ragged", false, convs, conv_dtype,
+                                   conv_extents, conv_strides, n_img, n_fields, layout, quad,
+                                   mirror, src_field, swap_ends, H, W, d_container, out_fields,
+                                   out_field0, d_tables, tables_bytes, stream);
+}
+
+int pp_fields_from_conv_ragged_interleaved(
+    const void *const *convs, int32_t conv_dtype, const int32_t *conv_extents,
+    const int64_t *conv_strides, int32_t n_img, int32_t n_fields, int32_t layout, int32_t quad,
+    int32_t mirror, const int32_t *src_field, const uint8_t *swap_ends, int32_t H, int32_t W,
+    float *d_container, int32_t out_fields, int32_t out_field0, void *d_tables,
+    size_t tables_bytes, void *stream) {
+    return fields_from_conv_ragged("pp_fields_from_conv_ragged_interleaved", true, convs,
+                                   conv_dtype, conv_extents, conv_strides, n_img, n_fields, layout,
+                                   quad, mirror, src_field, swap_ends, H, W, d_container,
+                                   out_fields, out_field0, d_tables, tables_bytes, stream);
 }
 
 }  // extern "C"

@@ -210,7 +210,8 @@ class RaggedFields:
                   cif_hflip=None, caf_hflip=None, caf_parts=None):
         """The same object from the heads' conv outputs, one HIP pass per head straight into
         the containers (heads.fields_from_conv_ragged has the forms `cif_convs` / `caf_convs`
-        and `conv_extents` take): no per-image fields and no pack.  `caf_parts`, a list of
+        and `conv_extents` take; NCHW and channels-last conv outputs and their slices are read
+        where they lie): no per-image fields and no pack.  `caf_parts`, a list of
         (convs, n_fields, hflip), replaces caf_convs / n_caf / caf_hflip: the parts are
         written side by side into one CAF container (CAF and dense CAF of the
         dense-connection layout).  pack() runs the ingest launches again."""

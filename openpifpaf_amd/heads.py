@@ -13,7 +13,8 @@ they lie, by their strides (pp_fields_from_conv_strided).
 `MultiScaleCollector` does that for the head list of a ShellMultiScale-style model
 (network/nets.py:95-143), whose second five scales come from the mirrored image.
 `fields_from_conv_ragged` / `RaggedCollector` ingest the conv outputs of images of different
-sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged);
+sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged, and
+pp_fields_from_conv_ragged_interleaved for channels-last conv outputs, read in place too);
 `RaggedDetCollector` does it for a detection head (engine.RaggedDetFields).
 """
 import ctypes
@@ -131,7 +132,8 @@ def fields_from_conv(conv, n_fields, kind, quad=1, hflip=None, out=None, out_fie
 
 class RaggedIngest:
     """One head's conv outputs of n images of different sizes and the container of a ragged
-    batch they are ingested into (pp_fields_from_conv_ragged): the pinned host tables, the
+    batch they are ingested into (pp_fields_from_conv_ragged, or for channels-last inputs
+    pp_fields_from_conv_ragged_interleaved: `interleaved`): the pinned host tables, the
     device tables and the output, built once; launch() enqueues the pass on the current
     stream, again after the conv tensors were rewritten in place.  The arguments are
     fields_from_conv_ragged's; `out_fields` widens a container allocated here.
@@ -145,17 +147,18 @@ class RaggedIngest:
         layout, n_out = LAYOUTS[kind]
         channels = n_fields * n_out * 4 ** quad
         if isinstance(convs, torch.Tensor):
-            ptrs, strides, ext, keep = self._batched(convs, conv_extents)
+            ptrs, strides, ext, keep, interleaved = self._batched(convs, conv_extents)
         else:
             if conv_extents is not None:
                 raise ValueError('conv_extents goes with one batched tensor; the tensors of a '
                                  'list have their own sizes')
-            ptrs, strides, ext, keep = self._listed(list(convs))
+            ptrs, strides, ext, keep, interleaved = self._listed(list(convs))
         first = keep[0]
         if first.shape[-3] != channels:
             raise ValueError('{} conv expects {} channels, got {}'.format(
                 kind, channels, first.shape[-3]))
         self._convs = keep  # the tables point into them
+        self.interleaved = interleaved
         self.n = n = len(ext)
         self.extents_host = ext.astype(np.int32)
         for _ in range(quad):  # pp_fields_dim
@@ -201,10 +204,20 @@ class RaggedIngest:
             raise ValueError('ragged conv outputs must be float32, float16 or bfloat16 device '
                              'tensors')
 
+    @staticmethod
+    def _readable(shape, stride):
+        """(planar, interleaved): whether a (ch, h, w) view is read where it lies by its column
+        stride 1 (pp_fields_from_conv_ragged) and by its channel stride 1
+        (pp_fields_from_conv_ragged_interleaved).  The stride of an extent of 1 says nothing."""
+        return shape[2] == 1 or stride[2] == 1, shape[0] == 1 or stride[0] == 1
+
     @classmethod
     def _listed(cls, convs):
-        """Per-image tensors (ch, h_i, w_i) or (1, ch, h_i, w_i): a view whose columns are not
-        adjacent (channels-last included) is copied, that image only."""
+        """Per-image tensors (ch, h_i, w_i) or (1, ch, h_i, w_i), classified once.  The call
+        is interleaved when some image is read by its channel stride alone (channels-last and
+        its slices) and none by its column stride alone; any other list is planar, as it was
+        before the interleaved symbol.  A view the call's class does not read is copied into
+        it, that image only."""
         if not convs:
             raise ValueError('a ragged batch needs at least one image')
         keep = []
@@ -215,22 +228,31 @@ class RaggedIngest:
             if t.dim() != 3:
                 raise ValueError('expected per-image conv outputs (ch, h, w) or (1, ch, h, w), '
                                  'got {}'.format(tuple(t.shape)))
-            if t.shape[2] > 1 and t.stride(2) != 1:
-                t = t.contiguous()
             keep.append(t)
         if any(t.dtype != keep[0].dtype or t.device != keep[0].device or
                t.shape[0] != keep[0].shape[0] for t in keep):
             raise ValueError('the conv outputs of a ragged batch differ in type, device or '
                              'channels')
+        kinds = [cls._readable(t.shape, t.stride()) for t in keep]
+        interleaved = (any(i and not p for p, i in kinds) and
+                       not any(p and not i for p, i in kinds))
+        if interleaved:
+            keep = [t if i else t.permute(1, 2, 0).contiguous().permute(2, 0, 1)
+                    for t, (_, i) in zip(keep, kinds)]
+            strides = np.array([t.stride()[1:] for t in keep], np.int64)
+        else:
+            keep = [t if p else t.contiguous() for t, (p, _) in zip(keep, kinds)]
+            strides = np.array([t.stride()[:2] for t in keep], np.int64)
         ptrs = np.array([t.data_ptr() for t in keep], np.uint64)
-        strides = np.array([t.stride()[:2] for t in keep], np.int64)
         ext = np.array([t.shape[1:] for t in keep], np.int64)
-        return ptrs, strides, ext, keep
+        return ptrs, strides, ext, keep, interleaved
 
     @classmethod
     def _batched(cls, conv, conv_extents):
         """One (n, ch, hmax, wmax) tensor whose image i is valid in [0, h_i) x [0, w_i):
-        pointers are base + i * image stride (no per-image data_ptr())."""
+        pointers are base + i * image stride (no per-image data_ptr()).  A channels-last
+        tensor, or a channel slice of one, is the interleaved call; a view that is neither
+        planar nor interleaved is copied once."""
         cls._check(conv)
         if conv.dim() != 4 or conv.shape[0] == 0:
             raise ValueError('expected a batched conv output (n, ch, hmax, wmax), n > 0')
@@ -242,12 +264,15 @@ class RaggedIngest:
         if ext.shape != (n, 2) or (ext <= 0).any() or (ext > np.array(conv.shape[2:])).any():
             raise ValueError('conv_extents must be (n, 2) rows (h_i, w_i) inside the batched '
                              'tensor, 0 < h_i <= {}, 0 < w_i <= {}'.format(*conv.shape[2:]))
-        if conv.shape[3] > 1 and conv.stride(3) != 1:
+        planar, interleaved = cls._readable(conv.shape[1:], conv.stride()[1:])
+        interleaved = interleaved and not planar
+        if not (planar or interleaved):
             conv = conv.contiguous()
         ptrs = (np.uint64(conv.data_ptr()) + np.arange(n, dtype=np.uint64) *
                 np.uint64(conv.stride(0) * conv.element_size()))
-        strides = np.tile(np.array(conv.stride()[1:3], np.int64), (n, 1))
-        return ptrs, strides, ext, [conv]
+        strides = np.tile(np.array(conv.stride()[2:] if interleaved else conv.stride()[1:3],
+                                   np.int64), (n, 1))
+        return ptrs, strides, ext, [conv], interleaved
 
     def launch(self):
         self.enqueue()
@@ -259,7 +284,8 @@ class RaggedIngest:
         n, size = self.n, self._tables.numel()
         dtype, n_fields, layout, quad, mirror = self._args
         host = self._host.data_ptr()
-        call('pp_fields_from_conv_ragged', ctypes.c_void_p(host), dtype,
+        call('pp_fields_from_conv_ragged_interleaved' if self.interleaved else
+             'pp_fields_from_conv_ragged', ctypes.c_void_p(host), dtype,
              ctypes.c_void_p(host + 24 * n), ctypes.c_void_p(host + 8 * n), n, n_fields, layout,
              quad, mirror, self._src_field, self._swap_ends, self.h, self.w,
              _device.ptr(self.out), self.out.shape[1], self.out_field0,
@@ -288,8 +314,13 @@ def fields_from_conv_ragged(convs, n_fields, kind, quad=1, hflip=None, conv_exte
     `convs` is a list of per-image device tensors (ch, h_i, w_i) or (1, ch, h_i, w_i), or one
     (n, ch, hmax, wmax) tensor with `conv_extents` (n, 2), the valid (h_i, w_i) of each image
     (a padded batch, or a channel slice of a fused one).  float32, float16 and bfloat16 are
-    read as they lie, by their channel and row strides; a view whose columns are not adjacent
-    (channels-last included) is copied once with .contiguous(), for a list that image only.
+    read as they lie: views whose columns are adjacent (NCHW and its slices) by their channel
+    and row strides, views whose channels are adjacent (channels-last and its channel and
+    spatial slices, e.g. contiguous(memory_format=channels_last)[0] or a permuted NHWC tensor)
+    by their row and column strides (pp_fields_from_conv_ragged_interleaved).  One call reads
+    one class: a list with images that only the first reads and images that only the second
+    reads is planar, and its channels-last images are copied, each once; a view that is
+    neither (a step along both channels and columns) is copied once into the call's class.
     `hflip` as in fields_from_conv; the mirror is about each image's own width.  `shape`
     (H, W) sets a container larger than the largest field size, which is the default.  With
     `out` (n, out_fields, 5 | 9 | 7, H, W) the fields go to out[:, out_field0:out_field0 +
