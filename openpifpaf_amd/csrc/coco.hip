@@ -15,8 +15,12 @@
 //                      a time, and one wave per kept record builds the record's 7 + 3 K
 //                      8-byte words in LDS (lane j = joint j, bbox by a wave reduction) and
 //                      stores them as contiguous 16-byte pairs
-// The per-record arithmetic is coco.hpp's, shared with the host twins (coco_cpu.hip).
+// The per-record arithmetic is coco.hpp's, shared with the host twins (coco_cpu.hip); its
+// inverse transform is inverse.hpp's, shared with the in-place kernels (inverse.hip).  The
+// packed offset, the 16-byte-pair store and the destination mapping are pack_common.hpp's,
+// shared with pack.hip.
 #include "coco.hpp"
+#include "pack_common.hpp"
 
 namespace pp {
 
@@ -24,40 +28,21 @@ namespace {
 
 struct CocoImage {  // what one workgroup knows about its image (LDS)
     pp_inverse_meta m;
-    CocoXf t;
+    InverseXf t;
     int src_of[PP_MAX_KP];
     int swap;
 };
 
-// meta, rotation constants and the swap's gather table of image `img`; ends with a barrier
+// meta, rotation constants and the swap's gather table of image `img`; the caller's next
+// barrier publishes them
 __device__ __forceinline__ void coco_image_setup(CocoImage &I, const pp_inverse_meta *metas,
                                                  const int *hswap, int K, int img) {
     if (threadIdx.x == 0) {
         I.m = metas[img];
-        I.t = coco_xf(I.m);
+        I.t = inverse_xf(I.m);
         I.swap = I.m.hflip && hswap != nullptr;
     }
     if (threadIdx.x < K && hswap) I.src_of[threadIdx.x] = coco_swap_source(hswap, K, threadIdx.x);
-    __syncthreads();
-}
-
-typedef uint64_t v2u __attribute__((ext_vector_type(2)));
-
-// `words` 8-byte words from LDS to dst (8-byte aligned) by one wave: a leading word when
-// dst is 8 mod 16, then 16-byte pairs, then a trailing word; words <= 128
-__device__ __forceinline__ void wave_store_words(uint64_t *dst, const uint64_t *src, int words,
-                                                 int lane) {
-    const int lead = (reinterpret_cast<uintptr_t>(dst) & 8) ? 1 : 0;
-    const int pairs = (words - lead) >> 1;
-    if (lane == 0 && lead) dst[0] = src[0];
-    v2u *dst2 = reinterpret_cast<v2u *>(dst + lead);
-    if (lane < pairs) {
-        v2u v;
-        v.x = src[lead + 2 * lane];
-        v.y = src[lead + 2 * lane + 1];
-        dst2[lane] = v;
-    }
-    if (lane == 0 && lead + 2 * pairs < words) dst[words - 1] = src[words - 1];
 }
 
 __device__ __forceinline__ float wave_min(float v) {
@@ -82,6 +67,7 @@ __global__ __launch_bounds__(256) void coco_count_kernel(const pp_ann *__restric
     const int img = blockIdx.x;
     if (threadIdx.x == 0) s_nan = 0;
     coco_image_setup(I, metas, hswap, K, img);
+    __syncthreads();
     const int n_rec = coco_clamp_count(counts[img], cap);
     const int *src_of = I.swap ? I.src_of : nullptr;
     int kept = 0;
@@ -117,13 +103,8 @@ __global__ __launch_bounds__(256) void coco_write_kernel(const pp_ann *__restric
     __shared__ uint64_t s_rec[4][kCocoHeadWords + 3 * PP_MAX_KP];
     const int img = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x == 0) s_off = 0;
     coco_image_setup(I, metas, hswap, K, img);
-    int part = 0;
-    for (int j = threadIdx.x; j < img; j += 256) part += ws_counts[j];
-    if (part) atomicAdd(&s_off, part);
-    __syncthreads();
-    const int64_t off = s_off;
+    const int64_t off = packed_offset(ws_counts, img, s_off);
     const int n_rec = coco_clamp_count(counts[img], cap);
     const int *src_of = I.swap ? I.src_of : nullptr;
     const int words = coco_record_words(K);
@@ -169,8 +150,8 @@ __global__ __launch_bounds__(256) void coco_write_kernel(const pp_ann *__restric
             wave_sync();
             const int64_t at = off + done + q;
             if (at < out_cap)
-                wave_store_words(reinterpret_cast<uint64_t *>(out + at * (8 * (int64_t)words)), w,
-                                 words, lane);
+                store_words(reinterpret_cast<uint64_t *>(out + at * (8 * (int64_t)words)), w, words,
+                            lane, 64);
             wave_sync();  // the wave's words are rewritten for its next record
         }
         done += m;
@@ -182,8 +163,8 @@ __global__ __launch_bounds__(256) void coco_write_kernel(const pp_ann *__restric
                           w[kCocoHeadWords + 3 * lane + 2] = u64_of(0.0);
         wave_sync();
         if (off < out_cap)
-            wave_store_words(reinterpret_cast<uint64_t *>(out + off * (8 * (int64_t)words)), w,
-                             words, lane);
+            store_words(reinterpret_cast<uint64_t *>(out + off * (8 * (int64_t)words)), w, words,
+                        lane, 64);
     }
 }
 
@@ -213,13 +194,8 @@ __global__ __launch_bounds__(256) void coco_det_write_kernel(const pp_det *__res
     __shared__ int s_off;
     __shared__ uint64_t s_w[256 * kCocoHeadWords];
     const int img = blockIdx.x;
-    if (threadIdx.x == 0) s_off = 0;
     coco_image_setup(I, metas, nullptr, 0, img);
-    int part = 0;
-    for (int j = threadIdx.x; j < img; j += 256) part += ws_counts[j];
-    if (part) atomicAdd(&s_off, part);
-    __syncthreads();
-    const int64_t off = s_off;
+    const int64_t off = packed_offset(ws_counts, img, s_off);
     const int64_t image_id = image_ids[img];
     const int kept = min(coco_clamp_count(counts[img], cap), P.max_per_image);
     const int n_out = kept > 0 ? kept : 1;
@@ -233,44 +209,11 @@ __global__ __launch_bounds__(256) void coco_det_write_kernel(const pp_det *__res
         __syncthreads();
         const int64_t first = off + base;
         const int64_t fit = min((int64_t)min(256, n_out - base), max((int64_t)0, out_cap - first));
-        uint64_t *dst = out + first * kCocoHeadWords;
-        const int words = (int)fit * kCocoHeadWords;
-        const int lead = (reinterpret_cast<uintptr_t>(dst) & 8) ? min(words, 1) : 0;
-        const int pairs = (words - lead) >> 1;
-        if (threadIdx.x == 0 && lead) dst[0] = s_w[0];
-        v2u *dst2 = reinterpret_cast<v2u *>(dst + lead);
-        for (int i = threadIdx.x; i < pairs; i += 256) {
-            v2u v;
-            v.x = s_w[lead + 2 * i];
-            v.y = s_w[lead + 2 * i + 1];
-            dst2[i] = v;
-        }
-        if (threadIdx.x == 0 && lead + 2 * pairs < words) dst[words - 1] = s_w[words - 1];
+        store_words(out + first * kCocoHeadWords, s_w, (int)fit * kCocoHeadWords, (int)threadIdx.x,
+                    256);
         __syncthreads();  // s_w is rewritten in the next round
     }
 }
-
-namespace {
-
-// destinations as the device sees them (device memory, or pinned host memory through its
-// mapped device address)
-int coco_destinations(const char *who, void **dst, int n) {
-    for (int i = 0; i < n; i++) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, dst[i]) != hipSuccess || !at.devicePointer ||
-            (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost)) {
-            (void)hipGetLastError();
-            return fail(PP_EINVAL, std::string(who) + ": destination is neither device memory "
-                                                      "nor pinned host memory");
-        }
-        dst[i] = at.devicePointer;
-    }
-    if (reinterpret_cast<uintptr_t>(dst[0]) & 7)
-        return fail(PP_EINVAL, std::string(who) + ": destination not 8-byte aligned");
-    return PP_OK;
-}
-
-}  // namespace
 
 }  // namespace pp
 
@@ -302,7 +245,9 @@ int pp_coco_keypoints(const pp_ann *d_anns, const int32_t *d_counts, int32_t n_i
         return fail(PP_EINVAL, "pp_coco_keypoints: destination not 8-byte aligned");
     if (n_img == 0) return PP_OK;
     void *dst[3] = {out, out_counts, out_flags};
-    if (const int rd = coco_destinations(who, dst, 3)) return rd;
+    if (const int rd = map_destinations(who, dst, 3)) return rd;
+    if (reinterpret_cast<uintptr_t>(dst[0]) & 7)  // the mapped address
+        return fail(PP_EINVAL, std::string(who) + ": destination not 8-byte aligned");
     hipLaunchKernelGGL(coco_count_kernel, dim3((unsigned)n_img), dim3(256), 0, (hipStream_t)stream,
                        d_anns, d_counts, capacity, K, d_metas, d_hswap, *params,
                        (int *)d_workspace, (int *)dst[1], (int *)dst[2]);
@@ -326,7 +271,9 @@ int pp_coco_dets(const pp_det *d_dets, const int32_t *d_counts, int32_t n_img, i
         return fail(PP_EINVAL, "pp_coco_dets: destination not 8-byte aligned");
     if (n_img == 0) return PP_OK;
     void *dst[3] = {out, out_counts, out_flags};
-    if (const int rd = coco_destinations(who, dst, 3)) return rd;
+    if (const int rd = map_destinations(who, dst, 3)) return rd;
+    if (reinterpret_cast<uintptr_t>(dst[0]) & 7)  // the mapped address
+        return fail(PP_EINVAL, std::string(who) + ": destination not 8-byte aligned");
     hipLaunchKernelGGL(coco_det_count_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, d_counts, n_img, capacity, *params,
                        (int *)d_workspace, (int *)dst[1], (int *)dst[2]);

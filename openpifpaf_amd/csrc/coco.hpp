@@ -1,10 +1,9 @@
 // coco.hpp — EvalCoco.from_predictions (eval_coco.py:108-158) per record: the pieces the
 // gfx950 kernels (coco.hip) and their host twins (coco_cpu.hip) share, so the two cannot
 // drift.  Every function is the reference's arithmetic in its order:
-//   - Preprocess.annotations_inverse (preprocess.py:35-95) as inverse.hip's
-//     ann_inverse_kernel / det_inverse_kernel state it (float32 rotation with the Python
-//     floats rounded, float64 offset / scale / hflip steps rounded to float32), here per
-//     joint and without writing the record back;
+//   - Preprocess.annotations_inverse (preprocess.py:35-95) from inverse.hpp, the statement
+//     inverse.hip's in-place kernels use, here per joint and without writing the record
+//     back;
 //   - Annotation.scale(v_th=0.01) (annotation.py:73-80), json_data (annotation.py:82-119)
 //     and AnnotationDet.json_data (annotation.py:138-145).
 // Rounding: a double that came from a float32 times 100.0 is exact (24 + 7 bits), so
@@ -12,13 +11,9 @@
 // scalar round(np.float64, 3) is multiply, rint, divide.
 #pragma once
 
-#include <math.h>
-
-#include "pp_common.hpp"
+#include "inverse.hpp"
 
 namespace pp {
-
-#define PP_HD __host__ __device__ __forceinline__
 
 // np.min / np.max of float32 values as a commutative, associative operation (so a wave
 // reduction and a sequential loop give the same bits): NaN propagates, and of two equal
@@ -34,11 +29,6 @@ PP_HD float coco_max(float a, float b) {
     return a > b ? a : b;
 }
 
-// np.minimum / np.maximum of two float32 scalars in rotate_box's order (inverse.hip's
-// npmin3 / npmax3)
-PP_HD float coco_npmin(float a, float b) { return (a != a || b != b) ? NAN : (a < b ? a : b); }
-PP_HD float coco_npmax(float a, float b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
-
 // np.around(float64(x), 2) == round(float(x), 2) of a float32 x.  A NaN comes out as the one
 // quiet NaN 0x7ff8000000000000: which sign and payload an operation hands on differs between
 // the host's and the device's arithmetic, and json prints every NaN alike.
@@ -53,45 +43,6 @@ PP_HD double coco_score3(double s) {
     return r > 0.001 ? r : 0.001;
 }
 
-// The rotation's constants of one image (preprocess.py:51-56): Python floats rounded to
-// float32 where NumPy multiplies them with the float32 arrays
-struct CocoXf {
-    float c, s, hw, hh;
-    int rot;
-};
-PP_HD CocoXf coco_xf(const pp_inverse_meta &m) {
-    CocoXf t{};
-    const double angle = -m.rotation_angle;
-    t.rot = angle != 0.0;
-    if (t.rot) {
-        t.c = (float)cos(angle / 180.0 * M_PI);
-        t.s = (float)sin(angle / 180.0 * M_PI);
-        t.hw = (float)((m.rotation_width - 1.0) / 2.0);
-        t.hh = (float)((m.rotation_height - 1.0) / 2.0);
-    }
-    return t;
-}
-
-// one joint's (x, y) through rotation, offset, scale; `nan` as the reference's assert sees
-// it (preprocess.py:67, before the flip); then the flip's x (preprocess.py:69-71)
-PP_HD void coco_point(const pp_inverse_meta &m, const CocoXf &t, float &x, float &y, float v,
-                      bool &nan) {
-    if (t.rot) {
-        const float xo = x - t.hw, yo = y - t.hh;
-        x = (t.hw + t.c * xo) + t.s * yo;
-        y = (t.hh - t.s * xo) + t.c * yo;
-    }
-    x = (float)((double)x + m.offset[0]);
-    y = (float)((double)y + m.offset[1]);
-    x = (float)((double)x / m.scale[0]);
-    y = (float)((double)y / m.scale[1]);
-    nan = nan || x != x || y != y || v != v;
-    if (m.hflip) x = (float)(-(double)x + (m.width - 1.0));
-}
-PP_HD float coco_jscale(const pp_inverse_meta &m, float s) {
-    return (float)((double)s / m.scale[0]);
-}
-
 // _HorizontalSwap as a gather (hflip.py:17-29 scatters source rows to hswap[source], last
 // writer wins, rows nobody writes stay zero): the source row of target row t, or -1
 PP_HD int coco_swap_source(const int *hswap, int K, int t) {
@@ -103,10 +54,10 @@ PP_HD int coco_swap_source(const int *hswap, int K, int t) {
 
 // Row j of the record's data after annotations_inverse, with joint j's scale; src_of
 // (K, or NULL without a swap) from coco_swap_source
-PP_HD void coco_row(const pp_ann &a, const pp_inverse_meta &m, const CocoXf &t, const int *src_of,
-                    int j, float &x, float &y, float &v, float &js) {
+PP_HD void coco_row(const pp_ann &a, const pp_inverse_meta &m, const InverseXf &t,
+                    const int *src_of, int j, float &x, float &y, float &v, float &js) {
     const int src = src_of ? src_of[j] : j;
-    js = coco_jscale(m, a.joint_scales[j]);
+    js = inverse_jscale(m, a.joint_scales[j]);
     if (src < 0) {
         x = y = v = 0.0f;
         return;
@@ -115,7 +66,7 @@ PP_HD void coco_row(const pp_ann &a, const pp_inverse_meta &m, const CocoXf &t, 
     y = a.data[src][1];
     v = a.data[src][2];
     bool nan = false;
-    coco_point(m, t, x, y, v, nan);
+    inverse_point(m, t, x, y, v, nan);
 }
 
 // Steps 1 and 2 of from_predictions for one record: whether it passes the small-object
@@ -123,13 +74,13 @@ PP_HD void coco_row(const pp_ann &a, const pp_inverse_meta &m, const CocoXf &t, 
 // NaN assert fires on it.  Annotation.scale(v_th=0.01) in float32 over the rows with
 // v > 0.01f, compared with the threshold in float32 (NEP 50); without such a row the scale
 // is the Python float 0.0, compared in float64.
-PP_HD bool coco_keep(const pp_ann &a, int K, const pp_inverse_meta &m, const CocoXf &t,
+PP_HD bool coco_keep(const pp_ann &a, int K, const pp_inverse_meta &m, const InverseXf &t,
                      const int *src_of, double small_threshold, bool &nan) {
     bool any = false;
     float x0 = 0.0f, x1 = 0.0f, y0 = 0.0f, y1 = 0.0f;
     for (int j = 0; j < K; j++) {  // the NaN test reads every source row
         float x = a.data[j][0], y = a.data[j][1];
-        coco_point(m, t, x, y, a.data[j][2], nan);
+        inverse_point(m, t, x, y, a.data[j][2], nan);
     }
     if (!(small_threshold != 0.0)) return true;
     for (int j = 0; j < K; j++) {
@@ -170,38 +121,11 @@ PP_HD void coco_dummy_head(int64_t image_id, int32_t second, uint64_t *w) {
     w[6] = coco_cat_word(1, second);
 }
 
-// anndet_inverse (preprocess.py:84-95) with rotate_box (transforms/utils.py:5-28) as
-// det_inverse_kernel states it, then AnnotationDet.json_data (annotation.py:138-145)
-PP_HD void coco_det_words(const pp_det &d, const pp_inverse_meta &m, const CocoXf &t,
+// anndet_inverse (inverse_box), then AnnotationDet.json_data (annotation.py:138-145)
+PP_HD void coco_det_words(const pp_det &d, const pp_inverse_meta &m, const InverseXf &t,
                           int64_t image_id, uint64_t *w) {
     float b[4] = {d.bbox[0], d.bbox[1], d.bbox[2], d.bbox[3]};
-    if (t.rot) {
-        const float cx[4] = {b[0], b[0] + b[2], b[0], b[0] + b[2]};
-        const float cy[4] = {b[1], b[1], b[1] + b[3], b[1] + b[3]};
-        float rx[4], ry[4];
-        for (int i = 0; i < 4; i++) {
-            const float xo = cx[i] - t.hw, yo = cy[i] - t.hh;
-            rx[i] = (t.hw + t.c * xo) + t.s * yo;
-            ry[i] = (t.hh - t.s * xo) + t.c * yo;
-        }
-        float x = rx[0], y = ry[0], xm = rx[0], ym = ry[0];
-        for (int i = 1; i < 4; i++) {
-            x = coco_npmin(x, rx[i]);
-            y = coco_npmin(y, ry[i]);
-            xm = coco_npmax(xm, rx[i]);
-            ym = coco_npmax(ym, ry[i]);
-        }
-        b[0] = x;
-        b[1] = y;
-        b[2] = xm - x;
-        b[3] = ym - y;
-    }
-    b[0] = (float)((double)b[0] + m.offset[0]);
-    b[1] = (float)((double)b[1] + m.offset[1]);
-    b[0] = (float)((double)b[0] / m.scale[0]);
-    b[1] = (float)((double)b[1] / m.scale[1]);
-    b[2] = (float)((double)b[2] / m.scale[0]);
-    b[3] = (float)((double)b[3] / m.scale[1]);
+    inverse_box(m, t, b);
     w[0] = (uint64_t)image_id;
     w[1] = u64_of(coco_score3((double)d.score));
     for (int i = 0; i < 4; i++) w[2 + i] = u64_of(coco_round2(b[i]));

@@ -42,7 +42,7 @@ int pp_coco_keypoints_cpu(const pp_ann *anns, const int32_t *counts, int32_t n_i
     int64_t at = 0;  // packed index of the next record
     for (int img = 0; img < n_img; img++) {
         const pp_inverse_meta &m = metas[img];
-        const CocoXf t = coco_xf(m);
+        const InverseXf t = inverse_xf(m);
         int table[PP_MAX_KP];
         const int *src_of = nullptr;
         if (m.hflip && hswap) {
@@ -107,7 +107,7 @@ int pp_coco_dets_cpu(const pp_det *dets, const int32_t *counts, int32_t n_img, i
     static_assert(sizeof(pp_coco_det) == 8 * kCocoHeadWords, "a detection record is the head words");
     int64_t at = 0;
     for (int img = 0; img < n_img; img++) {
-        const CocoXf t = coco_xf(metas[img]);
+        const InverseXf t = inverse_xf(metas[img]);
         const int n_rec = coco_clamp_count(counts[img], capacity);
         const int kept = n_rec < params->max_per_image ? n_rec : params->max_per_image;
         for (int r = 0; r < kept; r++) {

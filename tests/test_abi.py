@@ -400,3 +400,138 @@ def test_packed_record_size_matches_python_layout():
             assert packed_dtype(k, c, flags).itemsize % 16 == 0
     assert lib.pp_packed_record_size(0, 19, 3) == 0 and lib.pp_packed_record_size(17, 65, 3) == 0
     assert 2 * packed_dtype(17, 19, 3).itemsize < ANN_DTYPE.itemsize
+
+
+def _handover_refusal_calls():
+    """[(label, entry point, arguments)]: bad calls to the in-place inverse, the record packing
+    and the COCO record entry points.  Device pointers are a dummy non-NULL value; every case
+    stops at an argument check (or at the empty batch), before any HIP call."""
+    p, odd = ctypes.c_void_p(16), ctypes.c_void_p(17)
+    params, none = _abi.CocoParams(0.0, 20, 1), _abi.CocoParams(0.0, 0, 1)
+
+    def inverse(anns=p, n=1, cap=8, k=17, flags=p):
+        return [anns, p, n, cap, k, p, None, flags, None]
+
+    def dets(metas=p, n=1, cap=8):
+        return [p, p, n, cap, metas, None]
+
+    def records(out=p, n=1, cap=8, out_cap=8):
+        return [p, p, n, cap, out, out_cap, p, None]
+
+    def compact(counts=p, n=1, cap=8, k=17, c=19, flags=_abi.PACK_ALL, out_cap=8):
+        return [p, counts, n, cap, k, c, ctypes.c_uint32(flags), p, out_cap, p, None, None]
+
+    def coco(det, ids=p, n=1, cap=8, k=17, par=params, out=p, ws=p):
+        head = [p, p, n, cap] + ([] if det else [k]) + [p, ids] + ([] if det else [None])
+        return head + [ctypes.byref(par), out, 8, p, p, ws, None]
+
+    calls = [
+        ('inverse NULL anns', 'pp_annotations_inverse', inverse(anns=None)),
+        ('inverse NULL nan_flags', 'pp_annotations_inverse', inverse(flags=None)),
+        ('inverse n_img=-1', 'pp_annotations_inverse', inverse(n=-1)),
+        ('inverse capacity=0', 'pp_annotations_inverse', inverse(cap=0)),
+        ('inverse K=0', 'pp_annotations_inverse', inverse(k=0)),
+        ('inverse K=25', 'pp_annotations_inverse', inverse(k=25)),
+        ('inverse n_img=0', 'pp_annotations_inverse', inverse(n=0)),
+        ('dets NULL metas', 'pp_dets_inverse', dets(metas=None)),
+        ('dets n_img=-1', 'pp_dets_inverse', dets(n=-1)),
+        ('dets capacity=0', 'pp_dets_inverse', dets(cap=0)),
+        ('dets n_img=0', 'pp_dets_inverse', dets(n=0)),
+        ('records NULL out', 'pp_pack_records', records(out=None)),
+        ('records n_img=-1', 'pp_pack_records', records(n=-1)),
+        ('records capacity=0', 'pp_pack_records', records(cap=0)),
+        ('records out_capacity=-1', 'pp_pack_records', records(out_cap=-1)),
+        ('records n_img=0', 'pp_pack_records', records(n=0)),
+        ('compact NULL counts', 'pp_pack_compact', compact(counts=None)),
+        ('compact n_img=-1', 'pp_pack_compact', compact(n=-1)),
+        ('compact capacity=0', 'pp_pack_compact', compact(cap=0)),
+        ('compact K=0', 'pp_pack_compact', compact(k=0)),
+        ('compact K=25', 'pp_pack_compact', compact(k=25)),
+        ('compact C=65', 'pp_pack_compact', compact(c=65)),
+        ('compact unknown flag', 'pp_pack_compact', compact(flags=4)),
+        ('compact unknown flag and K=25', 'pp_pack_compact', compact(flags=4, k=25)),
+        ('compact n_img=0', 'pp_pack_compact', compact(n=0)),
+    ]
+    for name, det in (('pp_coco_keypoints', False), ('pp_coco_dets', True)):
+        tag = 'coco dets' if det else 'coco keypoints'
+        calls += [
+            (tag + ' NULL image_ids', name, coco(det, ids=None)),
+            (tag + ' n_img=-1', name, coco(det, n=-1)),
+            (tag + ' capacity=0', name, coco(det, cap=0)),
+            (tag + ' max_per_image=0', name, coco(det, par=none)),
+            (tag + ' NULL workspace', name, coco(det, ws=None)),
+            (tag + ' odd out', name, coco(det, out=odd)),
+            (tag + ' odd out and n_img=0', name, coco(det, out=odd, n=0)),
+            (tag + ' n_img=0', name, coco(det, n=0)),
+        ]
+    calls += [('coco keypoints K=0', 'pp_coco_keypoints', coco(False, k=0)),
+              ('coco keypoints K=25', 'pp_coco_keypoints', coco(False, k=25))]
+    return calls, [params, none]
+
+
+def _handover_refusals(lib):
+    calls, keep = _handover_refusal_calls()
+    out = []
+    for label, name, args in calls:
+        rc = getattr(lib, name)(*args)
+        out.append((label, rc, lib.pp_last_error().decode() if rc else None))
+    del keep
+    return out
+
+
+def test_handover_refusals_pinned(lib):
+    """Every argument refusal of pp_annotations_inverse, pp_dets_inverse, pp_pack_records,
+    pp_pack_compact, pp_coco_keypoints and pp_coco_dets, with its status and message as
+    recorded from the library before inverse.hip was cut into inverse.hpp, pack.hip and
+    pack_common.hpp: NULL arguments, n_img < 0, capacity 0, K 0 and 25, C 65, an unknown pack
+    flag, max_per_image 0, a NULL workspace, an odd `out` address.  Every refusal happens
+    before any HIP call, so no GPU is needed; an empty batch is PP_OK."""
+    got = _handover_refusals(lib)
+    assert [g[0] for g in got] == [r[0] for r in HANDOVER_REFUSALS]
+    for g, want in zip(got, HANDOVER_REFUSALS):
+        assert g == want
+
+
+HANDOVER_REFUSALS = [
+    ('inverse NULL anns', -1, 'pp_annotations_inverse: NULL argument'),
+    ('inverse NULL nan_flags', -1, 'pp_annotations_inverse: NULL argument'),
+    ('inverse n_img=-1', -2, 'pp_annotations_inverse: bad shape'),
+    ('inverse capacity=0', -2, 'pp_annotations_inverse: bad shape'),
+    ('inverse K=0', -2, 'pp_annotations_inverse: bad shape'),
+    ('inverse K=25', -2, 'pp_annotations_inverse: bad shape'),
+    ('inverse n_img=0', 0, None),
+    ('dets NULL metas', -1, 'pp_dets_inverse: NULL argument'),
+    ('dets n_img=-1', -2, 'pp_dets_inverse: bad shape'),
+    ('dets capacity=0', -2, 'pp_dets_inverse: bad shape'),
+    ('dets n_img=0', 0, None),
+    ('records NULL out', -1, 'pp_pack_records: NULL argument'),
+    ('records n_img=-1', -2, 'pp_pack_records: bad shape'),
+    ('records capacity=0', -2, 'pp_pack_records: bad shape'),
+    ('records out_capacity=-1', -2, 'pp_pack_records: bad shape'),
+    ('records n_img=0', 0, None),
+    ('compact NULL counts', -1, 'pp_pack_compact: NULL argument'),
+    ('compact n_img=-1', -2, 'pp_pack_compact: bad shape'),
+    ('compact capacity=0', -2, 'pp_pack_compact: bad shape'),
+    ('compact K=0', -2, 'pp_pack_compact: bad shape'),
+    ('compact K=25', -2, 'pp_pack_compact: bad shape'),
+    ('compact C=65', -2, 'pp_pack_compact: bad shape'),
+    ('compact unknown flag', -1, 'pp_pack_compact: unknown flag'),
+    ('compact unknown flag and K=25', -2, 'pp_pack_compact: bad shape'),
+    ('compact n_img=0', 0, None),
+]
+for _who in ('pp_coco_keypoints', 'pp_coco_dets'):
+    _tag = 'coco dets' if _who == 'pp_coco_dets' else 'coco keypoints'
+    HANDOVER_REFUSALS += [
+        (_tag + ' NULL image_ids', -1, _who + ': NULL argument'),
+        (_tag + ' n_img=-1', -2, _who + ': bad shape'),
+        (_tag + ' capacity=0', -2, _who + ': bad shape'),
+        (_tag + ' max_per_image=0', -2, _who + ': max_per_image < 1'),
+        (_tag + ' NULL workspace', -1, _who + ': NULL argument'),
+        (_tag + ' odd out', -1, _who + ': destination not 8-byte aligned'),
+        (_tag + ' odd out and n_img=0', -1, _who + ': destination not 8-byte aligned'),
+        (_tag + ' n_img=0', 0, None),
+    ]
+HANDOVER_REFUSALS += [
+    ('coco keypoints K=0', -2, 'pp_coco_keypoints: K outside [1, PP_MAX_KP]'),
+    ('coco keypoints K=25', -2, 'pp_coco_keypoints: K outside [1, PP_MAX_KP]'),
+]

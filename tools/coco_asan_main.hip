@@ -1,5 +1,6 @@
 // coco_asan_main.hip — sanitizer driver for the host twins of the COCO record kernels
-// (pp_coco_keypoints_cpu / pp_coco_dets_cpu, csrc/coco_cpu.hip with csrc/coco.hpp).  Host
+// (pp_coco_keypoints_cpu / pp_coco_dets_cpu, csrc/coco_cpu.hip with csrc/coco.hpp and the
+// inverse transform of csrc/inverse.hpp, which the in-place kernels share).  Host
 // code only, a program of its own; build and run where no GPU is needed:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host \

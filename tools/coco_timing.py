@@ -15,6 +15,8 @@ and min-max of --runs (>= 20).  One JSON line per route.
   batch+dicts the same plus CocoRecords.predictions() (the list of dicts)
   launches    pp_coco_keypoints alone (both launches) by HIP events, records written to
               device memory (`device`) or to mapped pinned memory (`pinned`)
+  inverse     transforms.inverse_records (pp_annotations_inverse, in place) by HIP events, on
+              a fresh device copy of the records made before the first event
 """
 import argparse
 import ctypes
@@ -117,16 +119,22 @@ def main():
              ctypes.c_void_p(o.data_ptr()), est, ctypes.c_void_p(h.data_ptr()),
              ctypes.c_void_p(h.data_ptr() + 4 * n), _device.ptr(ws), _device.stream())
 
+    def events_on_copy(fn):
+        recs = b.anns.view(n, b.cap, -1).clone()  # made before the first event
+        return events(lambda: fn(recs))
+
     routes = {
         'per-image': (wall, per_image),
         'batch': (wall, batch),
         'batch+dicts': (wall, lambda: batch().predictions()),
         'launches-device': (events, lambda: launches('device')),
         'launches-pinned': (events, lambda: launches('pinned')),
+        'inverse': (events_on_copy, lambda recs: transforms.inverse_records(
+            recs, b.counts, d_metas, k=k, hswap=d_swap)),
     }
     for _ in range(2):
-        for _, fn in routes.values():
-            fn()
+        for clock, fn in routes.values():
+            clock(fn)
     torch.cuda.synchronize()
     times = {name: [] for name in routes}
     for _ in range(args.runs):
