@@ -810,6 +810,62 @@ int pp_decode_ragged(const float *d_cif, const float *d_caf, int32_t n_img, int3
                      int32_t *d_status, void *d_workspace, size_t workspace_bytes,
                      uint32_t stages, void *stream);
 /*
+ * Ragged multi-scale batches: pp_decode_multi over images of different field sizes.
+ *
+ * Every pp_scale entry is a container (n_img, n_fields, channels, H, W) of its own (H, W),
+ * image i in the top-left corner of its planes at that head's own size.  The extent tables
+ * hold one (h, w) per entry and image, entry-major: (n_scales, n_img, 2) int32, so the
+ * sub-table of entry e starts at 2 * e * n_img.  d_extents is the device table, `extents` the
+ * same on the host (argument checks only, read before the call returns).
+ *
+ * pp_decode_multi_ragged: image i's records are, record for record and bit for bit, those of
+ * pp_decode_multi over that image alone with every head cropped to its own extent; pp_ann.image
+ * is its position in the batch.  In the reference the CifHr map takes its size from the first
+ * head filled (cif_hr.py:45-51), and the bounds of scalar_values (cif_seeds.py:37,
+ * caf_scored.py:63,74), the splat box clip and the occupancy grid (occupancy.py:11-26) follow
+ * the map: so image i's map is (h - 1) * stride + 1 of CIF head 0's extent, the sub-table of
+ * the entry that is CIF head 0, and the other heads' extents only say which container cells
+ * are real.  Precondition: the confidence channel (channel 0) of every cell outside its
+ * image's extent is 0 in every head, as the packers leave it.  Outputs, status bits, `stages`
+ * and the workspace contract are pp_decode_multi's at the containers' sizes
+ * (pp_decode_multi_workspace_size / _zero_offset / _work_offset).  With one CIF and one CAF
+ * entry of one (H, W) and stride it is pp_decode_ragged, byte for byte.
+ * Refused before anything touches HIP: PP_EINVAL for a NULL table, d_cifhr != NULL (no layout,
+ * as pp_decode_ragged), a negative cif_threshold, seed_threshold, caf_threshold or
+ * complete_caf_threshold, or a PP_ROLE_HRMAP entry (the map is CIF head 0's); PP_ESHAPE for an
+ * extent <= 0 or beyond its entry's (H, W).  n_img == 0 is PP_OK.  pp_decode_initial has no
+ * ragged form.
+ * Reference interface: openpifpaf.decoder.CifCaf.__call__ (cifcaf.py:67-122) per image.
+ *
+ * pp_fields_pack_ragged_heads fills the containers of all n_heads heads (at most
+ * 2 * PP_MAX_SCALES, in pp_scale entry order) in one launch.  HOST arguments: `fields`
+ * (n_heads, n_img) device pointers, head m's image i a contiguous float32
+ * (planes[m], h, w); `extents` (n_heads, n_img, 2); `planes` (n_heads) = n_fields * channels;
+ * `sizes` (n_heads, 2) the containers' (H, W); `d_containers` (n_heads) device pointers, each
+ * 4-byte aligned.  The two tables are copied into d_tables
+ * (pp_ragged_heads_tables_size(n_img, n_heads) bytes, 8-byte aligned) on the stream, pointers
+ * first, in ONE copy when `extents` lies right behind `fields` in host memory (at byte
+ * pp_ragged_heads_extents_offset(n_img, n_heads) of one block), else in two; afterwards the
+ * device extent table pp_decode_multi_ragged takes is at d_tables + that offset.  Host
+ * tables as for pp_fields_pack_ragged (pageable: consumed before the call returns; pinned:
+ * when the stream reaches the copy).  Every container element is written exactly once, as
+ * pp_fields_pack_ragged writes it, so no container needs a memset.  PP_ESHAPE: n_heads out of
+ * range, an extent <= 0 or larger than its head's container.  Both size functions return 0
+ * for n_img <= 0 or n_heads outside 1 .. 2 * PP_MAX_SCALES.
+ */
+size_t pp_ragged_heads_tables_size(int32_t n_img, int32_t n_heads);
+size_t pp_ragged_heads_extents_offset(int32_t n_img, int32_t n_heads);
+int pp_fields_pack_ragged_heads(const float *const *fields, const int32_t *extents, int32_t n_img,
+                                int32_t n_heads, const int32_t *planes, const int32_t *sizes,
+                                float *const *d_containers, void *d_tables, size_t tables_bytes,
+                                void *stream);
+int pp_decode_multi_ragged(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,
+                           int32_t n_img, int32_t K, int32_t C, const int32_t *d_extents,
+                           const int32_t *extents, const int32_t *skeleton, const pp_config *cfg,
+                           float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity,
+                           int32_t *d_counts, int32_t *d_status, void *d_workspace,
+                           size_t workspace_bytes, uint32_t stages, void *stream);
+/*
  * pp_cifdet_decode_ragged: pp_cifdet_decode over a ragged batch, one detection head without a
  * min scale.  d_det is the container (n_img, K, 7, H, W) (pp_fields_pack_ragged with channels
  * 7, or pp_fields_from_conv_ragged with layout 2, CifDet), d_extents / extents the device and

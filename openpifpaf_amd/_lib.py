@@ -178,6 +178,13 @@ _SIGNATURES = {
                               ctypes.c_int),
     'pp_decode_ragged': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                           _i32, _vp, _vp, _vp, _sz, _u32, _vp], ctypes.c_int),
+    # ... over the heads of a multi-scale FieldConfig
+    'pp_ragged_heads_tables_size': ([_i32, _i32], _sz),
+    'pp_ragged_heads_extents_offset': ([_i32, _i32], _sz),
+    'pp_fields_pack_ragged_heads': ([_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
+                                    ctypes.c_int),
+    'pp_decode_multi_ragged': ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _i32, _vp, _vp, _vp, _sz, _u32, _vp], ctypes.c_int),
     'pp_cifdet_ragged_workspace_size': ([_i32, _i32, _i32, _i32, _vp, _i32], _sz),
     'pp_cifdet_decode_ragged': ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                  _vp, _vp, _vp, _sz, _vp], ctypes.c_int),

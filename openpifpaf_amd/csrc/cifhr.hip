@@ -1336,11 +1336,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void c
     cifhr_sparse_body<MULTI, SEEDS>(a, nullptr, 0);
 }
 
-// one CIF head (the ragged decode is single-scale)
+// one CifHr group (a single-scale ragged decode, or several heads folded as one group)
 template <bool SEEDS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 void cifhr_sparse_ragged_kernel(HrSparseArgs a, const int32_t *ext, int K) {
     cifhr_sparse_body<false, SEEDS>(a, ext, K);
+}
+
+// several CifHr groups over a ragged batch (pp_decode_multi_ragged): the MULTI fold with the
+// image's own map size, which is CIF head 0's own (h_i - 1) * stride_0 + 1 (`ext` is that
+// head's (n_img, 2) table).  Every member's splat box at its own stride is clipped to that
+// map, the fold's and the aux map's "pixel is on the map" tests use it, and the groups
+// combine by np.maximum over it; cells of a member's container beyond its own extent hold
+// confidence 0 and splat nothing
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void cifhr_sparse_ragged_groups_kernel(HrSparseArgs a, const int32_t *ext, int K) {
+    cifhr_sparse_body<true, false>(a, ext, K);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1903,8 +1914,6 @@ int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_confi
     const HrMap geo = dense_hr(nullptr, hh, ww);
     if (geo.tiles > kTileBits) return fail(PP_ESHAPE, std::string(who) + ": CifHr map too large");
     if (h.n_groups > 8) return fail(PP_ESHAPE, std::string(who) + ": too many CifHr groups");
-    if (ext && (h.n_cif != 1 || h.n_groups != 1 || h.group_size() != 1))
-        return fail(PP_EINVAL, std::string(who) + ": a ragged batch has one CIF head");
     HrSparseArgs a{};
     a.h = h;
     a.hh = hh;
@@ -1998,7 +2007,9 @@ int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_confi
             hipLaunchKernelGGL(cifhr_list_kernel<false>, dim3((unsigned)nf), dim3(256), 0, s, a);
         }
     }
-    if (ext && sink)
+    if (ext && h.n_groups > 1)
+        hipLaunchKernelGGL(cifhr_sparse_ragged_groups_kernel, dim3(nblocks), dim3(256), 0, s, a, ext, K);
+    else if (ext && sink)
         hipLaunchKernelGGL(cifhr_sparse_ragged_kernel<true>, dim3(nblocks), dim3(256), 0, s, a, ext, K);
     else if (ext)
         hipLaunchKernelGGL(cifhr_sparse_ragged_kernel<false>, dim3(nblocks), dim3(256), 0, s, a, ext, K);

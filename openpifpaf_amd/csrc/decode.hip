@@ -6,7 +6,7 @@
 //   DecodeRegions / decode_regions: the workspace regions as typed pointers;
 //   grow_args: the GrowArgs of stage 8 (the skeleton through by_source.hpp's BySource);
 //   stamps_begin / stamps_end: the diagnostic build's buffers and their dump;
-//   decode_heads: the stage sequence, behind all five pp_decode_* entry points.
+//   decode_heads: the stage sequence, behind all six pp_decode_* entry points.
 #include "by_source.hpp"
 #include "grow_args.hpp"
 
@@ -248,7 +248,8 @@ struct DecodeInit {
     const int32_t *counts = nullptr;
     int32_t cap = 0;
     int32_t *out_index = nullptr;
-    // pp_decode_ragged: the images' own field sizes, device (n_img, 2) (hr_dims)
+    // pp_decode_ragged / pp_decode_multi_ragged: the images' own field sizes (of CIF head 0),
+    // device (n_img, 2) (hr_dims)
     const int32_t *extents = nullptr;
 };
 
@@ -441,7 +442,7 @@ static void stamps_begin(GrowArgs &, int, hipStream_t) {}
 static void stamps_end(const GrowArgs &, int, hipStream_t) {}
 #endif
 
-// The stage sequence of a decode, behind all five entry points.
+// The stage sequence of a decode, behind all six entry points.
 static int decode_heads(const Heads &h, int32_t n_img, int32_t K, int32_t C,
                         const int32_t *skeleton, const pp_config *cfg, float *d_cifhr,
                         pp_ann *d_anns, int32_t ann_capacity, int32_t *d_counts,
@@ -613,6 +614,46 @@ int pp_decode_multi(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,
     if (rc) return rc;
     return decode_heads(h, n_img, K, C, skeleton, cfg, d_cifhr, d_anns, ann_capacity, d_counts,
                         d_status, d_workspace, workspace_bytes, stages, stream);
+}
+
+int pp_decode_multi_ragged(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs,
+                           int32_t n_img, int32_t K, int32_t C, const int32_t *d_extents,
+                           const int32_t *extents, const int32_t *skeleton, const pp_config *cfg,
+                           float *d_cifhr, pp_ann *d_anns, int32_t ann_capacity,
+                           int32_t *d_counts, int32_t *d_status, void *d_workspace,
+                           size_t workspace_bytes, uint32_t stages, void *stream) {
+    if (!cfg || !d_extents || !extents)
+        return fail(PP_EINVAL, "pp_decode_multi_ragged: NULL argument");
+    if (d_cifhr)
+        return fail(PP_EINVAL, "pp_decode_multi_ragged: the dense CifHr map of a ragged batch has "
+                               "no layout (d_cifhr must be NULL)");
+    Heads h;
+    const int rc = make_heads(scales, n_scales, cif_pairs, 3, &h, "pp_decode_multi_ragged");
+    if (rc) return rc;
+    // the map is CIF head 0's: the kernels take every image's own map size from that head's
+    // sub-table (hr_dims), first = the entry that is CIF head 0
+    int first = -1;
+    for (int e = 0; e < n_scales; e++) {
+        if (scales[e].role == PP_ROLE_HRMAP)
+            return fail(PP_EINVAL, "pp_decode_multi_ragged: a ragged batch takes no PP_ROLE_HRMAP "
+                                   "entry (the map is CIF head 0's)");
+        if (first < 0 && (scales[e].role == 0 || (scales[e].role & PP_ROLE_CIF))) first = e;
+    }
+    // cells outside an extent hold confidence 0 and every threshold compare is c > th: they
+    // are candidates of nothing as long as no threshold is negative
+    if (cfg->cif_threshold < 0.0f || cfg->seed_threshold < 0.0f || cfg->caf_threshold < 0.0f ||
+        cfg->complete_caf_threshold < 0.0f)
+        return fail(PP_EINVAL, "pp_decode_multi_ragged: a ragged batch needs thresholds >= 0");
+    for (int e = 0; e < n_scales; e++)
+        for (int i = 0; i < n_img; i++) {
+            const int32_t *x = extents + 2 * ((int64_t)e * n_img + i);
+            if (x[0] <= 0 || x[0] > scales[e].H || x[1] <= 0 || x[1] > scales[e].W)
+                return fail(PP_ESHAPE, "pp_decode_multi_ragged: extent outside the container");
+        }
+    DecodeInit init;
+    init.extents = d_extents + 2 * (int64_t)first * std::max(n_img, 0);
+    return decode_heads(h, n_img, K, C, skeleton, cfg, nullptr, d_anns, ann_capacity, d_counts,
+                        d_status, d_workspace, workspace_bytes, stages, stream, init);
 }
 
 int pp_decode_initial(const pp_scale *scales, int32_t n_scales, int32_t cif_pairs, int32_t n_img,

@@ -365,7 +365,8 @@ struct HrMap {
     }
 };
 
-// Ragged batches (pp_decode_ragged): the images of one batch share a container (H, W) and
+// Ragged batches (pp_decode_ragged; pp_decode_multi_ragged: a container per head, `ext` the
+// table of CIF head 0, whose map it is): the images of one batch share a container (H, W) and
 // every storage geometry derived from it (pitch, tiles, occupancy pitch, bucket grid), and
 // an (n_img, 2) device table `ext` holds each image's own field size (h_i, w_i).  The
 // image's own CifHr size decides three things only: the bounds of scalar_values
@@ -528,7 +529,8 @@ SeedSink seed_sink(int n_img, int K, const pp_config *cfg, int cap, void *scratc
 bool cifhr_fuses_seeds(const Heads &h, int n_img, int K, const pp_config *cfg);
 
 // `sink` (NULL: none): emit the seeds too (cifhr_fuses_seeds must hold); `ext` (NULL: none):
-// a ragged batch's extent table (hr_dims; one CIF head)
+// a ragged batch's extent table (hr_dims): CIF head 0's (n_img, 2) sizes, whose map every group
+// folds into (several groups: cifhr_sparse_ragged_groups_kernel)
 int cifhr_sparse_launch(const Heads &h, int32_t n_img, int32_t K, const pp_config *cfg,
                         float *d_map, float *d_aux, uint64_t *d_masks, void *d_workspace,
                         size_t workspace_bytes, hipStream_t s, const char *who,

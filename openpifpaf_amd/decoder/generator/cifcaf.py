@@ -18,7 +18,8 @@ from ... import _device, _edges, functional
 from ..._abi import PACK_ALL, check_seed_mask, make_config, skeleton_array
 from ...annotation import Annotation
 from ...distributed import decode_sharded, shard
-from ...engine import HeadSet, InitialAnnotations, RaggedFields, engine
+from ...engine import (HeadSet, InitialAnnotations, RaggedFields, RaggedHeadSet,
+                       check_head_lists, engine)
 from ...functional import _edge_call, grow_connection_blend
 from .. import nms as nms_module
 from ..caf_scored import CafScored
@@ -274,8 +275,9 @@ class CifCaf(Generator):
 
     # -- ragged batches: images of different field sizes -----------------------------------
     def _ragged(self, fields_list, kw):
-        """RaggedFields of a list of per-image head lists (Generator.fields_batch entries, each
-        read through the single-scale FieldConfig), packed on the device."""
+        """RaggedFields (single-scale FieldConfig) or RaggedHeadSet (any other) of a list of
+        per-image head lists (Generator.fields_batch entries, each read through the
+        FieldConfig), packed on the device."""
         for name in ('group', 'initial_annotations', 'keep_cifhr'):
             if kw.pop(name, None):
                 raise NotImplementedError(
@@ -283,11 +285,17 @@ class CifCaf(Generator):
                     'the seeds and keeps no dense CifHr map'.format(name))
         if kw:
             raise TypeError('unexpected arguments: ' + ', '.join(sorted(kw)))
-        if not self.field_config.is_single_scale():
-            raise NotImplementedError('a ragged batch needs a single-scale FieldConfig (one '
-                                      'CIF and one CAF head); multi-scale heads are not built')
-        if isinstance(fields_list, RaggedFields):  # packed or ingested already
+        if isinstance(fields_list, (RaggedFields, RaggedHeadSet)):  # packed or ingested already
+            if isinstance(fields_list, RaggedFields) != self.field_config.is_single_scale():
+                raise TypeError('a single-scale FieldConfig decodes a RaggedFields, a '
+                                'multi-scale one a RaggedHeadSet')
             return fields_list
+        if not self.field_config.is_single_scale():
+            check_head_lists(self.field_config)  # before anything goes to the device
+            used = set(self.field_config.cif_indices) | set(self.field_config.caf_indices)
+            return RaggedHeadSet([[_device.to_device(h) if i in used else None
+                                   for i, h in enumerate(f)] for f in fields_list],
+                                 self.field_config)
         cif_i, caf_i, _ = self.field_config.single_scale()
         return RaggedFields([(_device.to_device(f[cif_i]), _device.to_device(f[caf_i]))
                              for f in fields_list])
@@ -296,9 +304,11 @@ class CifCaf(Generator):
         """One entry per image, each image's head outputs [cif (K, 5, h_i, w_i), caf (C, 9,
         h_i, w_i), ...] at its OWN size (what Generator.fields_batch returns, from any
         number of forward passes) -> one list of Annotation per image, each as __call__
-        gives it for that image alone, decoded as one device batch (pp_decode_ragged).  An
-        engine.RaggedFields (e.g. RaggedFields.from_conv, heads.RaggedCollector) in place of
-        the list is decoded as it is."""
+        gives it for that image alone, decoded as one device batch (pp_decode_ragged).  With a
+        multi-scale FieldConfig every head of an image has its own size and the batch takes
+        pp_decode_multi_ragged.  An engine.RaggedFields (e.g. RaggedFields.from_conv,
+        heads.RaggedCollector) or, multi-scale, an engine.RaggedHeadSet in place of the list
+        is decoded as it is."""
         ragged = self._ragged(fields_list, kw)
         recs, offsets, _ = engine().decode(None, None, skeleton_array(self.skeleton),
                                            self.config(), compact=PACK_ALL, ragged=ragged)

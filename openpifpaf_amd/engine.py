@@ -332,6 +332,122 @@ class RaggedDetFields:
              _device.stream())
 
 
+def check_head_lists(fc):
+    """A multi-scale FieldConfig for a ragged batch names every head in every per-head list.
+    The reference walks the lists with zip (cif_hr.py:69-78, cif_seeds.py:57-59,
+    caf_scored.py:88-98), so a list shorter than cif_indices / caf_indices silently drops the
+    heads behind it there: the default min-scale and distance lists of one entry beside two
+    heads decode head 0 alone.  That truncation is not built for ragged batches."""
+    nc, na = len(fc.cif_indices), len(fc.caf_indices)
+    short = [name for name, want in (('cif_strides', nc), ('cif_min_scales', nc),
+                                     ('caf_strides', na), ('caf_min_distances', na),
+                                     ('caf_max_distances', na))
+             if len(getattr(fc, name)) != want]
+    if nc == 0 or na == 0 or short:
+        raise NotImplementedError(
+            'a ragged batch needs a single-scale FieldConfig, or a multi-scale one with one '
+            'entry per head in every list: {} CIF and {} CAF heads, but {}'.format(
+                nc, na, ', '.join('{} has {}'.format(name, len(getattr(fc, name)))
+                                  for name in short) or 'no head of one kind'))
+
+
+class RaggedHeadSet:
+    """A batch of images of different field sizes under a multi-scale FieldConfig
+    (pp_fields_pack_ragged_heads, pp_decode_multi_ragged): `fields_list` is one head list per
+    image (what Generator.fields_batch returns), each head a float32 contiguous device tensor
+    at its own size, CIF heads (K, 5, h, w) and CAF heads (C, 9, h, w), K and C the same for
+    every head and image; `field_config` names the heads.  Packs all heads in one launch on
+    the current stream into one container per head, (n, K, 5, H_m, W_m) / (n, C, 9, H_m, W_m)
+    with (H_m, W_m) head m's largest size, zero outside each image's extent, and owns them
+    (`cifs`, `cafs`) with the pp_scale array `arr` over them, the pinned host tables and the
+    entry-major extent table (`extents`, device (n_heads, n, 2) int32, CIF heads first;
+    `extents_host` the same on the host).  `shape_key` names the containers' shapes for the
+    engine's buffer cache.  The images' tensors may be freed once the pack has run."""
+
+    def __init__(self, fields_list, field_config):
+        lib = load()
+        fc = field_config
+        fields_list = [list(f) for f in fields_list]
+        if not fields_list:
+            raise ValueError('a ragged batch needs at least one image')
+        check_head_lists(fc)
+        nc, na = len(fc.cif_indices), len(fc.caf_indices)
+        index = list(fc.cif_indices) + list(fc.caf_indices)
+        top = max(index)
+        if any(len(f) <= top for f in fields_list):
+            raise ValueError('an image has {} heads, the FieldConfig reads head {}'.format(
+                min(len(f) for f in fields_list), top))
+        # heads[m][i]: head m (CIF heads, then CAF heads: the pp_scale entry order) of image i.
+        # One pass over the n_heads * n tensors collects what the tables need; the shapes are
+        # then checked as one array
+        heads = [[f[j] for f in fields_list] for j in index]
+        f32, tensor = torch.float32, torch.Tensor
+        shapes, ptrs = [], []
+        for row in heads:
+            for t in row:
+                if not (isinstance(t, tensor) and t.is_cuda and t.dtype == f32
+                        and t.is_contiguous()):
+                    raise ValueError('ragged heads must be contiguous float32 device tensors '
+                                     '(K, 5, h, w) and (C, 9, h, w)')
+                shapes.append(t.shape)
+                ptrs.append(t.data_ptr())
+        self.n = n = len(fields_list)
+        n_heads = nc + na
+        if any(len(sh) != 4 for sh in shapes):
+            raise ValueError('ragged heads must be contiguous float32 device tensors '
+                             '(K, 5, h, w) and (C, 9, h, w)')
+        shapes = np.array(shapes, np.int64).reshape(n_heads, n, 4)
+        if (shapes[:nc, :, 1] != 5).any() or (shapes[nc:, :, 1] != 9).any():
+            raise ValueError('expected CIF heads (K, 5, h, w) and CAF heads (C, 9, h, w)')
+        self.k, self.c = int(shapes[0, 0, 0]), int(shapes[nc, 0, 0])
+        if (shapes[:nc, :, 0] != self.k).any() or (shapes[nc:, :, 0] != self.c).any():
+            raise ValueError('the heads of a ragged batch differ in K or C: K in {}, C in {}'.format(
+                sorted(set(shapes[:nc, :, 0].reshape(-1).tolist())),
+                sorted(set(shapes[nc:, :, 0].reshape(-1).tolist()))))
+        self.extents_host = np.ascontiguousarray(shapes[:, :, 2:], np.int32)
+        sizes = self.extents_host.max(axis=1)  # (n_heads, 2): the containers' (H, W)
+        dev = heads[0][0].device
+        outs = [torch.empty((n, row[0].shape[0], row[0].shape[1], int(hw[0]), int(hw[1])),
+                            dtype=torch.float32, device=dev) for row, hw in zip(heads, sizes)]
+        self.cifs, self.cafs = outs[:nc], outs[nc:]
+        self.h, self.w = int(sizes[0][0]), int(sizes[0][1])
+        self.stride0 = int(fc.cif_strides[0])
+        self.pairs = int(nc == 10)  # cif_hr.py:63
+        self.arr = scale_list([(t.data_ptr(), t.shape[3], t.shape[4]) for t in self.cifs],
+                              [(t.data_ptr(), t.shape[3], t.shape[4]) for t in self.cafs],
+                              fc.cif_strides, fc.caf_strides, fc.cif_min_scales,
+                              fc.caf_min_distances, fc.caf_max_distances)
+        self.shape_key = ('ragged', self.pairs) + tuple(
+            (s.H, s.W, s.stride, s.role) for s in self.arr)
+        # one pinned host block: pointers, extents (both copied to the device in one piece),
+        # then the per-head planes, container sizes and container pointers the call reads;
+        # the copy is asynchronous, so the block lives as long as this object
+        size = lib.pp_ragged_heads_tables_size(n, n_heads)
+        ext_off = lib.pp_ragged_heads_extents_offset(n, n_heads)
+        self._size, self._ext_off, self._n_heads = size, ext_off, n_heads
+        self._host = torch.empty(size + 20 * n_heads, dtype=torch.uint8, pin_memory=True)
+        self._tables = torch.empty(size, dtype=torch.uint8, device=dev)
+        host = self._host.numpy()
+        host[:ext_off].view(np.uint64)[:] = ptrs
+        host[ext_off:size].view(np.int32)[:] = self.extents_host.reshape(-1)
+        tail = host[size:]
+        tail[:8 * n_heads].view(np.uint64)[:] = [t.data_ptr() for t in outs]
+        tail[8 * n_heads:12 * n_heads].view(np.int32)[:] = [t.shape[1] * t.shape[2] for t in outs]
+        tail[12 * n_heads:].view(np.int32)[:] = sizes.reshape(-1)
+        self.extents = self._tables[ext_off:].view(torch.int32).view(n_heads, n, 2)
+        self.pack()
+
+    def pack(self):
+        """The pack launch on the current stream, from the tables built at construction: again
+        after the images' tensors were rewritten in place."""
+        base, size, nh = self._host.data_ptr(), self._size, self._n_heads
+        call('pp_fields_pack_ragged_heads', ctypes.c_void_p(base),
+             ctypes.c_void_p(base + self._ext_off), self.n, nh,
+             ctypes.c_void_p(base + size + 8 * nh), ctypes.c_void_p(base + size + 12 * nh),
+             ctypes.c_void_p(base + size), _device.ptr(self._tables), ctypes.c_size_t(size),
+             _device.stream())
+
+
 def _buffer_key(n, k, c, shape, cap, cfg):
     return (n, k, c, shape, cap, cfg.force_complete, cfg.stride, cfg.occupancy_reduction)
 
@@ -421,6 +537,20 @@ class DecodeEngine:
              _device.stream())
         return b
 
+    def launch_ragged_multi(self, ragged, skeleton, cfg, cap=None, stages=STAGE_ALL):
+        """pp_decode_multi_ragged over a RaggedHeadSet, with launch_multi's buffers at the
+        containers' shapes; returns the DecodeBuffers."""
+        n, k, c = ragged.n, ragged.k, ragged.c
+        skel, cap, b = self._prepare(skeleton, n, k, c, ragged.h, ragged.w, cfg, cap, stages,
+                                     ragged)
+        call('pp_decode_multi_ragged', ragged.arr, len(ragged.arr), ragged.pairs, n, k, c,
+             _device.ptr(ragged.extents), ragged.extents_host.ctypes.data_as(ctypes.c_void_p),
+             skel.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cfg), ctypes.c_void_p(0),
+             _device.ptr(b.anns), cap, _device.ptr(b.counts), _device.ptr(b.status),
+             _device.ptr(b.ws), ctypes.c_size_t(b.ws.numel()), ctypes.c_uint32(stages),
+             _device.stream())
+        return b
+
     def launch_multi(self, heads, skeleton, cfg, cap=None, keep_cifhr=False, stages=STAGE_ALL,
                      initial=None):
         """pp_decode_multi over a HeadSet (pp_decode_initial with `initial`); returns the
@@ -441,13 +571,14 @@ class DecodeEngine:
 
     def launch_checked(self, cif, caf, skeleton, cfg, cap=None, keep_cifhr=False, heads=None,
                        initial=None, ragged=None):
-        """launch / launch_multi / launch_ragged with overflow retry (the annotation capacity
-        doubles until no image overflows); returns the DecodeBuffers of a decode whose
-        records are complete.  Raises PPError on the overflows a retry cannot fix.  With a
-        RaggedFields `ragged`, cif / caf are ignored."""
+        """launch / launch_multi / launch_ragged / launch_ragged_multi with overflow retry (the
+        annotation capacity doubles until no image overflows); returns the DecodeBuffers of a
+        decode whose records are complete.  Raises PPError on the overflows a retry cannot
+        fix.  With a RaggedFields or RaggedHeadSet `ragged`, cif / caf are ignored."""
         if ragged is not None:
             if heads is not None:
-                raise NotImplementedError('a ragged batch is single-scale (no HeadSet)')
+                raise NotImplementedError('a ragged batch carries its own heads (a '
+                                          'RaggedHeadSet as `ragged`), no HeadSet beside it')
             if initial is not None:
                 raise NotImplementedError('a ragged batch takes no initial annotations')
             if keep_cifhr:
@@ -459,7 +590,9 @@ class DecodeEngine:
         cap = cap or default_ann_capacity(h, w)
         stages = STAGE_ALL | (STAGE_NMS_WIDE if self.density >= _B_FIRST_DENSITY else 0)
         while True:
-            if ragged is not None:
+            if isinstance(ragged, RaggedHeadSet):
+                b = self.launch_ragged_multi(ragged, skeleton, cfg, cap=cap, stages=stages)
+            elif ragged is not None:
                 b = self.launch_ragged(ragged, skeleton, cfg, cap=cap, stages=stages)
             elif heads is None:
                 b = self.launch(cif, caf, skeleton, cfg, cap=cap, keep_cifhr=keep_cifhr,
@@ -487,8 +620,9 @@ class DecodeEngine:
         HeadSet `heads`, cif / caf are ignored and the multi-scale decode runs.  `compact`
         flags (e.g. _abi.PACK_ALL) fetch compact records (pp_pack_compact) instead of full
         pp_ann records.  `initial` (InitialAnnotations): grown before the seed loop; the
-        buffers then hold out_index (see pp_decode_initial).  `ragged` (RaggedFields): the
-        images decode at their own sizes (pp_decode_ragged); cif / caf are ignored."""
+        buffers then hold out_index (see pp_decode_initial).  `ragged` (RaggedFields, or a
+        RaggedHeadSet for a multi-scale FieldConfig): the images decode at their own sizes
+        (pp_decode_ragged / pp_decode_multi_ragged); cif / caf are ignored."""
         b = self.launch_checked(cif, caf, skeleton, cfg, cap=cap, keep_cifhr=keep_cifhr,
                                 heads=heads, initial=initial, ragged=ragged)
         k = ragged.k if ragged is not None else cif.shape[1] if heads is None else heads.k
