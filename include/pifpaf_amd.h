@@ -637,6 +637,76 @@ int pp_fields_from_conv_ragged_interleaved(const void *const *convs, int32_t con
         int32_t out_field0, void *d_tables, size_t tables_bytes, void *stream);
 
 /*
+ * pp_fields_from_conv_ragged for every head of a multi-scale FieldConfig in ONE launch: the
+ * conv outputs of n_entries heads of n_img images go straight into the containers of a ragged
+ * head set (pp_decode_multi_ragged), with no per-image fields, no pack and no memset.  An
+ * entry (pp_conv_head) is one conv head and the field range of one container it writes;
+ * several entries may write side by side into one container (CAF and dense CAF).  For every
+ * entry the bytes of its field range are those of pp_fields_from_conv_ragged called for that
+ * entry alone: inside image i's own field bit for bit pp_fields_from_conv_ex of the image
+ * alone, mirrored about its own width, +0 outside it, every element stored exactly once, the
+ * container's other fields untouched.
+ *   heads         HOST (n_entries), 1 <= n_entries <= 3 * PP_MAX_SCALES.  layout 0 CIF or
+ *                 1 CAF; d_container (n_img, out_fields, 5 | 9, H, W) float32, 4-byte aligned;
+ *                 ext_row = the row of the field extent table the entry writes, or -1: every
+ *                 row 0 .. n_rows - 1 is named by exactly one entry.  mirror, has_src,
+ *                 src_field and swap_mask are pp_fields_from_conv_ex's mirror, src_field and
+ *                 swap_ends; pp_conv_head_set_flip fills them from that call's arguments
+ *                 (n_fields and layout set beforehand) with that call's checks.
+ *   convs, conv_extents, conv_strides
+ *                 HOST, entry-major (n_entries, n_img), (n_entries, n_img, 2) and
+ *                 (n_entries, n_img, 2) or NULL, per (entry, image) what
+ *                 pp_fields_from_conv_ragged takes per image (the planar class: column
+ *                 stride 1).  The entries of one container have the same conv extents.
+ *   conv_dtype, quad   of every conv output
+ *   d_tables      pp_ragged_conv_heads_tables_size(n_img, n_entries) bytes, 8-byte aligned:
+ *                 the pointers (8 n_entries n_img bytes), the strides (16 ...), the entries
+ *                 (sizeof(pp_conv_head) n_entries), the conv extents (8 ...), then, at
+ *                 pp_ragged_conv_heads_extents_offset(n_img, n_entries), the (n_rows, n_img, 2)
+ *                 int32 FIELD extent table the kernel writes, row r = the (H_i, W_i) of the
+ *                 entry that names r: the layout pp_decode_multi_ragged takes.  The host
+ *                 tables go there in one copy on the stream when they lie in one host block in
+ *                 this order (conv_strides given), else in one copy per table.  Pageable host
+ *                 tables are consumed before the call returns, pinned ones when the stream
+ *                 reaches the copy.  No device memory is allocated.
+ * Workgroups of entry 0 come first on the x grid, then entry 1's (a prefix table of workgroup
+ * counts in the kernel arguments); the image is the y grid.  Checked before any copy or launch,
+ * in this order: a NULL table -> PP_EINVAL; n_img < 0, n_entries outside 1 .. 3 *
+ * PP_MAX_SCALES, n_rows outside 1 .. n_entries, quad outside 0 .. 4 -> PP_ESHAPE; an unknown
+ * dtype -> PP_EINVAL; per entry a NULL container -> PP_EINVAL, n_fields, H or W <= 0 ->
+ * PP_ESHAPE, a layout other than 0 or 1 -> PP_EINVAL, and the checks of pp_fields_from_conv_ex
+ * on the flip tables and the field range with its codes, H * W or n_img * out_fields * channels
+ * beyond int32 -> PP_ESHAPE, a misaligned container -> PP_EINVAL; more than 65535 images or
+ * 2^31 - 1 workgroups -> PP_ESHAPE; an ext_row outside -1 .. n_rows - 1, a row named by no
+ * entry or by two -> PP_EINVAL; two entries whose container ranges overlap, or that share a
+ * container but not its (layout, H, W, out_fields) -> PP_EINVAL; per (entry, image) the
+ * pointer, extent and stride checks of pp_fields_from_conv_ragged with its codes; entries of
+ * one container with different conv extents for some image -> PP_ESHAPE; then, for n_img > 0,
+ * a table buffer too small -> PP_ENOMEM and d_tables not 8-byte aligned -> PP_EINVAL.
+ * n_img = 0 returns PP_OK after the checks.  Offsets are 64-bit.
+ */
+typedef struct pp_conv_head {
+    float *d_container;
+    int32_t layout, n_fields;
+    int32_t H, W;                     /* the container's */
+    int32_t out_fields, out_field0;
+    int32_t ext_row;
+    int32_t mirror, has_src;
+    int32_t reserved;                 /* 0 */
+    uint64_t swap_mask;               /* bit f: swap_ends[f] */
+    uint8_t src_field[64];
+} pp_conv_head;
+int pp_conv_head_set_flip(pp_conv_head *head, int32_t mirror, const int32_t *src_field,
+                          const uint8_t *swap_ends);
+size_t pp_ragged_conv_heads_tables_size(int32_t n_img, int32_t n_entries);
+size_t pp_ragged_conv_heads_extents_offset(int32_t n_img, int32_t n_entries);
+int pp_fields_from_conv_ragged_heads(const pp_conv_head *heads, int32_t n_entries,
+                                     int32_t n_rows, const void *const *convs,
+                                     const int32_t *conv_extents, const int64_t *conv_strides,
+                                     int32_t n_img, int32_t conv_dtype, int32_t quad,
+                                     void *d_tables, size_t tables_bytes, void *stream);
+
+/*
  * nms.Keypoints.annotations (nms.py:17-57) over caller records, n_img independent groups:
  * d_anns (n_img, ann_capacity) with d_counts[i] records in group i (modified in place as
  * the reference modifies its Annotation objects: joints below keypoint_threshold zeroed,

@@ -206,6 +206,24 @@ class DetNms(ctypes.Structure):
                 ('iou_threshold_soft', ctypes.c_float), ('apply', ctypes.c_int32)]
 
 
+class ConvHead(ctypes.Structure):
+    """pp_conv_head: one conv head of pp_fields_from_conv_ragged_heads and the field range of
+    the container it writes.  CONV_HEAD_DTYPE is the same row for NumPy."""
+    _fields_ = [('d_container', ctypes.c_void_p), ('layout', ctypes.c_int32),
+                ('n_fields', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('out_fields', ctypes.c_int32), ('out_field0', ctypes.c_int32),
+                ('ext_row', ctypes.c_int32), ('mirror', ctypes.c_int32),
+                ('has_src', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('swap_mask', ctypes.c_uint64), ('src_field', ctypes.c_uint8 * 64)]
+
+
+CONV_HEAD_DTYPE = np.dtype([('d_container', '<u8'), ('layout', '<i4'), ('n_fields', '<i4'),
+                            ('H', '<i4'), ('W', '<i4'), ('out_fields', '<i4'),
+                            ('out_field0', '<i4'), ('ext_row', '<i4'), ('mirror', '<i4'),
+                            ('has_src', '<i4'), ('reserved', '<i4'), ('swap_mask', '<u8'),
+                            ('src_field', 'u1', (64,))])
+
+
 ROLE_CIF, ROLE_CAF, ROLE_HRMAP = 1, 2, 4
 
 

@@ -130,6 +130,12 @@ _SIGNATURES = {
     'pp_fields_from_conv_ragged_interleaved': ([_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                                 _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz,
                                                 _vp], ctypes.c_int),
+    # ... of every head of a multi-scale FieldConfig in one launch (csrc/ingest_heads.hip)
+    'pp_conv_head_set_flip': ([_vp, _i32, _vp, _vp], ctypes.c_int),
+    'pp_ragged_conv_heads_tables_size': ([_i32, _i32], _sz),
+    'pp_ragged_conv_heads_extents_offset': ([_i32, _i32], _sz),
+    'pp_fields_from_conv_ragged_heads': ([_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp,
+                                         _sz, _vp], ctypes.c_int),
     'pp_nms_keypoints': ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
                          ctypes.c_int),
     'pp_nms_keypoints_scored': ([_vp, _vp, _i32, _i32, _i32, _vp, _f64, _vp, _vp, _vp, _vp,

@@ -362,7 +362,9 @@ class RaggedHeadSet:
     (`cifs`, `cafs`) with the pp_scale array `arr` over them, the pinned host tables and the
     entry-major extent table (`extents`, device (n_heads, n, 2) int32, CIF heads first;
     `extents_host` the same on the host).  `shape_key` names the containers' shapes for the
-    engine's buffer cache.  The images' tensors may be freed once the pack has run."""
+    engine's buffer cache.  The images' tensors may be freed once the pack has run.
+    RaggedHeadSet.from_conv builds the same object from the heads' conv outputs, without
+    per-image fields and without the pack."""
 
     def __init__(self, fields_list, field_config):
         lib = load()
@@ -437,9 +439,133 @@ class RaggedHeadSet:
         self.extents = self._tables[ext_off:].view(torch.int32).view(n_heads, n, 2)
         self.pack()
 
+    _ingests = ()  # from_conv: the heads.RaggedIngest of each part, or one RaggedHeadsIngest
+    _extents_pinned = None  # from_conv by a call per head: the host's extent table, pinned
+
+    @staticmethod
+    def _entry_parts(entry):
+        """One item of from_conv's `entries` as a list of parts (convs, n_fields, hflip)."""
+        from .heads import HFlip  # pylint: disable=import-outside-toplevel
+        if isinstance(entry, torch.Tensor):
+            return [(entry, None, None)]
+        if (isinstance(entry, tuple) and len(entry) == 2 and
+                (entry[1] is None or isinstance(entry[1], HFlip))):
+            return [(entry[0], None, entry[1])]
+        if (isinstance(entry, (list, tuple)) and entry and
+                all(isinstance(p, tuple) and len(p) == 3 for p in entry)):
+            return list(entry)
+        return [(entry, None, None)]
+
+    @classmethod
+    def from_conv(cls, entries, field_config, quad=1, conv_extents=None, one_launch=False):
+        """The same object from the heads' conv outputs, ingested straight into the containers:
+        no per-image fields and no pack.
+
+        `entries` is the model's head list, indexed as `field_config.cif_indices` /
+        `caf_indices` index it.  An item is the head's convs, or (convs, hflip) with a
+        heads.HFlip (heads.cif_hflip / caf_hflip) for a head of a mirrored pass; a CAF item may
+        also be a list of parts (convs, n_fields, hflip) written side by side into one
+        container (CAF and dense CAF).  `convs` is a list of per-image device tensors
+        (ch, h_i, w_i) / (1, ch, h_i, w_i), or one batched (n, ch, hmax, wmax) tensor with
+        `conv_extents` (n, 2), the forms heads.fields_from_conv_ragged takes.  float32, float16
+        and bfloat16 are read as they lie, NCHW views and their channel, batch and row slices
+        in place.  Every head has its own sizes; the images have the same K and C.
+
+        The default is one pp_fields_from_conv_ragged call per head (heads.RaggedIngest),
+        which measured faster than the one-launch form (DESIGN.md "Ragged multi-scale
+        ingest"); it reads channels-last heads in place as well.  `one_launch` takes
+        pp_fields_from_conv_ragged_heads (heads.RaggedHeadsIngest): one pinned host block and
+        one library call for all heads.  There a channels-last view (or any view whose columns
+        are not adjacent) is copied once into NCHW, that tensor only: the one-launch form has
+        no channels-last kernel.  pack() runs the launches again, for use after the convs were
+        rewritten in place."""
+        from .heads import RaggedHeadsIngest, RaggedIngest  # pylint: disable=import-outside-toplevel
+        fc = field_config
+        check_head_lists(fc)
+        entries = list(entries)
+        nc = len(fc.cif_indices)
+        index = list(fc.cif_indices) + list(fc.caf_indices)
+        if len(entries) <= max(index):
+            raise ValueError('the model has {} heads, the FieldConfig reads head {}'.format(
+                len(entries), max(index)))
+        groups = [cls._entry_parts(entries[j]) for j in index]
+        self = cls.__new__(cls)
+        if one_launch:
+            ingest = RaggedHeadsIngest(
+                [(convs, n_fields, 'cif' if g < nc else 'caf', hflip, g)
+                 for g, parts in enumerate(groups) for convs, n_fields, hflip in parts],
+                quad, conv_extents)
+            self._ingests = [ingest]
+            outs, self.extents, self.extents_host = ingest.outs, ingest.extents, ingest.extents_host
+        else:
+            self._ingests, outs = [], []
+            for g, parts in enumerate(groups):
+                kind, per_field = ('cif', 5 * 4 ** quad) if g < nc else ('caf', 9 * 4 ** quad)
+                counts = [p[1] if p[1] is not None else cls._channels(p[0]) // per_field
+                          for p in parts]
+                first, done = None, 0
+                for (convs, _, hflip), n_fields in zip(parts, counts):
+                    ing = RaggedIngest(convs, n_fields, kind, quad, hflip, conv_extents,
+                                       out=first.out if first else None, out_field0=done,
+                                       out_fields=sum(counts))
+                    if first is None:
+                        first = ing
+                        outs.append(ing.out)
+                    elif not np.array_equal(ing.extents_host, first.extents_host):
+                        raise ValueError('the parts of one container differ in conv size')
+                    done += n_fields
+                    # launched at once: the device works while the host builds the next head
+                    self._ingests.append(ing.launch())
+            sizes = sorted({i.n for i in self._ingests})
+            if len(sizes) != 1:
+                raise ValueError('the heads of a ragged batch have different numbers of '
+                                 'images: ' + ', '.join(str(s) for s in sizes))
+            firsts = [i for i in self._ingests if i.out_field0 == 0]
+            self.extents_host = np.ascontiguousarray(np.stack([i.extents_host for i in firsts]))
+            # the per-head calls write a table each: the joint one comes from the host's
+            self._extents_pinned = torch.from_numpy(self.extents_host).pin_memory()
+            self.extents = torch.empty(self.extents_host.shape, dtype=torch.int32,
+                                       device=outs[0].device)
+            self.extents.copy_(self._extents_pinned, non_blocking=True)
+        self.n = self._ingests[0].n
+        self.cifs, self.cafs = outs[:nc], outs[nc:]
+        self.k, self.c = self.cifs[0].shape[1], self.cafs[0].shape[1]
+        if any(t.shape[1] != self.k for t in self.cifs) or any(t.shape[1] != self.c
+                                                               for t in self.cafs):
+            raise ValueError('the heads of a ragged batch differ in K or C: K in {}, C in {}'.format(
+                sorted({t.shape[1] for t in self.cifs}), sorted({t.shape[1] for t in self.cafs})))
+        self.h, self.w = self.cifs[0].shape[3], self.cifs[0].shape[4]
+        self.stride0 = int(fc.cif_strides[0])
+        self.pairs = int(nc == 10)  # cif_hr.py:63
+        self.arr = scale_list([(t.data_ptr(), t.shape[3], t.shape[4]) for t in self.cifs],
+                              [(t.data_ptr(), t.shape[3], t.shape[4]) for t in self.cafs],
+                              fc.cif_strides, fc.caf_strides, fc.cif_min_scales,
+                              fc.caf_min_distances, fc.caf_max_distances)
+        self.shape_key = ('ragged', self.pairs) + tuple(
+            (s.H, s.W, s.stride, s.role) for s in self.arr)
+        if one_launch:
+            self.pack()
+        return self
+
+    @staticmethod
+    def _channels(convs):
+        """The channel count of a head's convs (a batched tensor or a list of per-image ones)."""
+        if isinstance(convs, torch.Tensor):
+            return convs.shape[1] if convs.dim() == 4 else 0
+        convs = list(convs)
+        ok = convs and isinstance(convs[0], torch.Tensor) and convs[0].dim() >= 3
+        return convs[0].shape[-3] if ok else 0
+
     def pack(self):
         """The pack launch on the current stream, from the tables built at construction: again
-        after the images' tensors were rewritten in place."""
+        after the images' tensors were rewritten in place.  After from_conv: the ingest
+        launches."""
+        for ingest in self._ingests:
+            ingest.launch()
+        if self._ingests:
+            if self._extents_pinned is not None:
+                self.extents.copy_(self._extents_pinned, non_blocking=True)
+            return
         base, size, nh = self._host.data_ptr(), self._size, self._n_heads
         call('pp_fields_pack_ragged_heads', ctypes.c_void_p(base),
              ctypes.c_void_p(base + self._ext_off), self.n, nh,

@@ -16,6 +16,8 @@ they lie, by their strides (pp_fields_from_conv_strided).
 sizes straight into the containers of a ragged batch (pp_fields_from_conv_ragged, and
 pp_fields_from_conv_ragged_interleaved for channels-last conv outputs, read in place too);
 `RaggedDetCollector` does it for a detection head (engine.RaggedDetFields).
+`RaggedHeadsIngest` / `RaggedMultiScaleCollector` ingest every head of a multi-scale model, all
+images, in one launch (pp_fields_from_conv_ragged_heads, engine.RaggedHeadSet.from_conv).
 """
 import ctypes
 
@@ -331,6 +333,240 @@ def fields_from_conv_ragged(convs, n_fields, kind, quad=1, hflip=None, conv_exte
     ing = RaggedIngest(convs, n_fields, kind, quad, hflip, conv_extents, shape, out,
                        out_field0).launch()
     return ing.out, ing.extents, ing.extents_host
+
+
+def _planar_views(convs, conv_extents):
+    """The conv outputs of one head as pp_fields_from_conv_ragged_heads reads them: pointers
+    (n) uint64, channel and row strides (n, 2) int64, conv extents (n, 2) int64, the channel
+    counts (n), the type, the device and the tensors the pointers lead into.  `convs` and
+    `conv_extents` are fields_from_conv_ragged's.  Everything is collected in one pass over
+    the tensors and checked afterwards as arrays.  A view whose columns are not adjacent
+    (channels-last, or a step along the columns) is copied once into NCHW, that tensor only."""
+    if isinstance(convs, torch.Tensor):
+        RaggedIngest._check(convs)
+        if convs.dim() != 4 or convs.shape[0] == 0:
+            raise ValueError('expected a batched conv output (n, ch, hmax, wmax), n > 0')
+        if convs.shape[3] > 1 and convs.stride(3) != 1:
+            convs = convs.contiguous()
+        n = convs.shape[0]
+        ext = (np.tile(np.array(convs.shape[2:], np.int64), (n, 1)) if conv_extents is None
+               else np.asarray(conv_extents, dtype=np.int64))
+        if ext.shape != (n, 2) or (ext <= 0).any() or (ext > np.array(convs.shape[2:])).any():
+            raise ValueError('conv_extents must be (n, 2) rows (h_i, w_i) inside the batched '
+                             'tensor, 0 < h_i <= {}, 0 < w_i <= {}'.format(*convs.shape[2:]))
+        ptrs = (np.uint64(convs.data_ptr()) + np.arange(n, dtype=np.uint64) *
+                np.uint64(convs.stride(0) * convs.element_size()))
+        strides = np.tile(np.array(convs.stride()[1:3], np.int64), (n, 1))
+        channels = np.full(n, convs.shape[1], np.int64)
+        return ptrs, strides, ext, channels, convs.dtype, convs.device, [convs]
+    if conv_extents is not None:
+        raise ValueError('conv_extents goes with one batched tensor; the tensors of a list have '
+                         'their own sizes')
+    convs = list(convs)
+    if not convs:
+        raise ValueError('a ragged batch needs at least one image')
+    shapes, strides, ptrs, keep, kinds = [], [], [], [], set()
+    tensor = torch.Tensor
+    for t in convs:
+        if not (isinstance(t, tensor) and t.is_cuda):
+            raise ValueError('ragged conv outputs must be float32, float16 or bfloat16 device '
+                             'tensors')
+        sh, st = t.shape, t.stride()
+        if len(sh) == 4 and sh[0] == 1:
+            sh, st = sh[1:], st[1:]
+        if len(sh) != 3:
+            raise ValueError('expected per-image conv outputs (ch, h, w) or (1, ch, h, w), '
+                             'got {}'.format(tuple(t.shape)))
+        if sh[2] > 1 and st[2] != 1:
+            t = t.contiguous()
+            st = t.stride()[-3:]
+        shapes.append(sh)
+        strides.append(st[:2])
+        ptrs.append(t.data_ptr())
+        kinds.add((t.dtype, t.device))
+        keep.append(t)
+    if len(kinds) != 1 or keep[0].dtype not in _DTYPES:
+        raise ValueError('the conv outputs of a ragged batch must be of one type (float32, '
+                         'float16 or bfloat16) and on one device')
+    shapes = np.array(shapes, np.int64)
+    return (np.array(ptrs, np.uint64), np.array(strides, np.int64), shapes[:, 1:], shapes[:, 0],
+            keep[0].dtype, keep[0].device, keep)
+
+
+class RaggedHeadsIngest:
+    """The conv outputs of several heads of n images of different sizes and the containers of
+    a ragged head set they are ingested into in one launch (pp_fields_from_conv_ragged_heads):
+    one pinned host block, the device tables and the containers, built once; launch()
+    enqueues the pass on the current stream, again after the conv tensors were rewritten in
+    place.
+
+    `parts` is a list of (convs, n_fields, kind, hflip, group): `convs` and `conv_extents` as
+    fields_from_conv_ragged takes them, `n_fields` (None: what the channels say), `kind` 'cif'
+    or 'caf', `hflip` an HFlip or None, `group` the container the part writes.  The groups are
+    numbered from 0 in the order of their first part; the parts of one group are of one kind,
+    have the same conv sizes and lie side by side in its container, in their order.
+    `outs` maps a group to a container of the caller's, a contiguous float32 device tensor
+    (n, out_fields, 5 | 9, H, W) that holds every field size of the group, and `field0` a
+    group to the first field its parts write (0): the fields of the container outside the
+    group's range are left alone.
+
+    outs          per group the container (n, fields of the group, 5 | 9, H_g, W_g), (H_g, W_g)
+                  the group's largest field size
+    extents       device (n_groups, n, 2) int32 field sizes, written by the launch
+    extents_host  the same table, NumPy"""
+
+    def __init__(self, parts, quad=1, conv_extents=None, outs=None, field0=None):
+        from ._abi import CONV_HEAD_DTYPE  # pylint: disable=import-outside-toplevel
+        lib = load()
+        parts = list(parts)
+        views = [_planar_views(p[0], conv_extents) for p in parts]
+        counts = sorted({len(v[0]) for v in views})
+        if len(counts) != 1:
+            raise ValueError('the heads of a ragged batch have different numbers of images: ' +
+                             ', '.join(str(c) for c in counts))
+        self.n = n = counts[0]
+        n_entries = len(parts)
+        if len({(v[4], v[5]) for v in views}) != 1:
+            raise ValueError('the conv outputs of a ragged batch differ in type or device')
+        dtype, dev = views[0][4], views[0][5]
+        self._convs = [v[6] for v in views]  # the tables point into them
+        ext = np.stack([v[2] for v in views])  # (n_entries, n, 2) conv sizes
+        field_ext = ext.astype(np.int32)
+        for _ in range(quad):  # pp_fields_dim
+            field_ext = 2 * field_ext - 1
+        rows, groups = [], {}
+        for m, ((_, n_fields, kind, hflip, group), v) in enumerate(zip(parts, views)):
+            layout, n_out = LAYOUTS[kind]
+            per_field = n_out * 4 ** quad
+            channels = v[3]
+            if n_fields is None:
+                n_fields = int(channels[0]) // per_field
+            if n_fields <= 0 or (channels != n_fields * per_field).any():
+                raise ValueError('{} conv of {} fields expects {} channels, got {}: the images '
+                                 'of a ragged batch may not differ in K or C'.format(
+                                     kind, n_fields, n_fields * per_field,
+                                     sorted(set(channels.tolist()))))
+            g = groups.setdefault(group, dict(kind=kind, first=m, members=[],
+                                              fields=int((field0 or {}).get(group, 0))))
+            if g['kind'] != kind:
+                raise ValueError('the parts of one container are of one kind')
+            if not np.array_equal(ext[g['first']], ext[m]):
+                raise ValueError('the parts of one container differ in conv size')
+            rows.append((m, layout, n_fields, g['fields'], hflip, g))
+            g['fields'] += n_fields
+            g['members'].append(m)
+        self.extents_host = np.ascontiguousarray(
+            np.stack([field_ext[g['first']] for g in groups.values()]))
+        n_rows = len(groups)
+        self.outs = []
+        for r, g in enumerate(groups.values()):
+            h, w = (int(v) for v in self.extents_host[r].max(axis=0))
+            n_out = LAYOUTS[g['kind']][1]
+            out = (outs or {}).get(list(groups)[r])
+            if out is None:
+                out = torch.empty((n, g['fields'], n_out, h, w), dtype=torch.float32, device=dev)
+            elif (not _device.is_device(out) or out.dtype != torch.float32 or out.dim() != 5
+                  or not out.is_contiguous() or out.device != dev
+                  or tuple(out.shape[::2]) != (n, n_out, out.shape[4]) or g['fields'] < 0
+                  or out.shape[1] < g['fields'] or out.shape[3] < h or out.shape[4] < w):
+                raise ValueError('out must be a contiguous float32 device tensor (n, out_fields, '
+                                 '{}, H, W) that holds fields ..{} of {} x {}'.format(
+                                     n_out, g['fields'] - 1, h, w))
+            g['row'], g['hw'] = r, tuple(out.shape[3:])
+            self.outs.append(out)
+        # one pinned host block in the order of the device tables: pointers, strides, entries,
+        # conv extents; the field extents the kernel writes follow on the device
+        size = lib.pp_ragged_conv_heads_tables_size(n, n_entries)
+        ext_off = lib.pp_ragged_conv_heads_extents_offset(n, n_entries)
+        cells = n_entries * n
+        off = (0, 8 * cells, 24 * cells, 24 * cells + CONV_HEAD_DTYPE.itemsize * n_entries)
+        if size == 0 or off[3] + 8 * cells != ext_off:
+            raise ValueError('{} conv heads of {} images: outside what '
+                             'pp_fields_from_conv_ragged_heads takes'.format(n_entries, n))
+        self._host = torch.empty(ext_off, dtype=torch.uint8, pin_memory=True)
+        host = self._host.numpy()
+        host[:off[1]].view(np.uint64)[:] = np.concatenate([v[0] for v in views])
+        host[off[1]:off[2]].view(np.int64)[:] = np.concatenate([v[1] for v in views]).reshape(-1)
+        host[off[3]:].view(np.int32)[:] = ext.reshape(-1)
+        heads = host[off[2]:off[3]].view(CONV_HEAD_DTYPE)
+        heads[:] = np.zeros((), CONV_HEAD_DTYPE)
+        base = self._host.data_ptr()
+        for m, layout, n_fields, field0, hflip, g in rows:
+            out = self.outs[g['row']]
+            heads[m]['d_container'] = out.data_ptr()
+            heads[m]['layout'], heads[m]['n_fields'] = layout, n_fields
+            heads[m]['H'], heads[m]['W'] = g['hw']
+            heads[m]['out_fields'], heads[m]['out_field0'] = out.shape[1], field0
+            heads[m]['ext_row'] = g['row'] if m == g['first'] else -1
+            if hflip is not None:
+                src_field, swap_ends = hflip.tables(n_fields)
+                call('pp_conv_head_set_flip',
+                     ctypes.c_void_p(base + off[2] + CONV_HEAD_DTYPE.itemsize * m), 1, src_field,
+                     swap_ends)
+        self._off = off
+        self._args = (n_entries, n_rows, _DTYPES[dtype], quad)
+        self._tables = torch.empty(size, dtype=torch.uint8, device=dev)
+        self.extents = self._tables[ext_off:ext_off + 8 * n_rows * n].view(torch.int32).view(
+            n_rows, n, 2)
+
+    def launch(self):
+        self.enqueue()
+        _hold(self)
+        return self
+
+    def enqueue(self):
+        """The library call alone; the caller keeps this object until the stream is past it."""
+        n_entries, n_rows, dtype, quad = self._args
+        base, off = self._host.data_ptr(), self._off
+        call('pp_fields_from_conv_ragged_heads', ctypes.c_void_p(base + off[2]), n_entries,
+             n_rows, ctypes.c_void_p(base), ctypes.c_void_p(base + off[3]),
+             ctypes.c_void_p(base + off[1]), self.n, dtype, quad, _device.ptr(self._tables),
+             ctypes.c_size_t(self._tables.numel()), _device.stream())
+
+
+class RaggedMultiScaleCollector(torch.nn.Module):
+    """MultiScaleCollector for images of different sizes: forward(convs, conv_extents=None) ->
+    engine.RaggedHeadSet, every head of every image ingested in one launch
+    (engine.RaggedHeadSet.from_conv).  The constructor takes MultiScaleCollector's arguments
+    and the `field_config` that names the heads.  `convs` holds per scale `cif, caf[, dense
+    caf]`, the unflipped scales first, then the mirrored ones, which are un-flipped in the same
+    pass; each is a list of per-image tensors or one batched tensor with `conv_extents`
+    (fields_from_conv_ragged).  With a `dense_skeleton` the dense CAF is written behind the CAF
+    into one container (the `concat_dense` layout, the only one a FieldConfig with one CAF
+    index per scale names), so the head list has `cif, caf` per scale."""
+
+    def __init__(self, keypoints, skeleton, field_config, dense_skeleton=None, quad=1,
+                 n_scales=5, include_hflip=True, concat_dense=False):
+        super().__init__()
+        if concat_dense and dense_skeleton is None:
+            raise ValueError('concat_dense needs a dense_skeleton')
+        self.field_config = field_config
+        self.n_cif, self.n_caf = len(keypoints), len(skeleton)
+        self.n_dense = 0 if dense_skeleton is None else len(dense_skeleton)
+        self.quad, self.n_scales, self.include_hflip = quad, n_scales, include_hflip
+        self.cif_flip = cif_hflip(keypoints)
+        self.caf_flip = caf_hflip(keypoints, skeleton)
+        self.dense_flip = caf_hflip(keypoints, dense_skeleton) if self.n_dense else None
+
+    def forward(self, *args, conv_extents=None):  # pylint: disable=arguments-differ
+        from .engine import RaggedHeadSet  # pylint: disable=import-outside-toplevel
+        convs = args[0]
+        per = 3 if self.n_dense else 2
+        n = self.n_scales * (2 if self.include_hflip else 1)
+        if len(convs) != per * n:
+            raise ValueError('expected {} conv outputs ({} per scale), got {}'.format(
+                per * n, per, len(convs)))
+        entries = []
+        for s in range(n):
+            flipped = s >= self.n_scales
+            entries.append((convs[per * s], self.cif_flip if flipped else None))
+            caf = [(convs[per * s + 1], self.n_caf, self.caf_flip if flipped else None)]
+            if self.n_dense:
+                caf.append((convs[per * s + 2], self.n_dense,
+                            self.dense_flip if flipped else None))
+            entries.append(caf)
+        return RaggedHeadSet.from_conv(entries, self.field_config, self.quad,
+                                       conv_extents=conv_extents)
 
 
 class RaggedCollector(torch.nn.Module):
