@@ -756,6 +756,25 @@ int pp_pack_records(const pp_ann *d_anns, const int32_t *d_counts, int32_t n_img
                     void *stream);
 
 /*
+ * The same hand-over for the detection decoder: d_dets (n_img, det_capacity) pp_det with
+ * d_counts[i] valid records in row i, as every pp_cifdet_decode* entry point writes them,
+ * packed image after image into `out`, the counts copied to out_counts and, when d_status
+ * and out_status are given (together, or both NULL: PP_EINVAL otherwise), the decode's
+ * PP_ST_* status words to out_status -- all in one launch, so one stream synchronisation
+ * hands the caller the records and what it needs to judge them (an overflow bit means a
+ * decode at a larger capacity).  `out`, `out_counts` and `out_status` may be device memory
+ * or pinned host memory, as for pp_pack_records.  d_dets and `out` are 16-byte aligned
+ * (PP_EINVAL otherwise, also for an empty batch): a pp_det is copied as two 16-byte chunks.
+ * Records whose packed index is >= out_capacity are not written; out_counts is always
+ * complete.  No more than det_capacity records of a row are read, whatever its count.
+ * n_img == 0 is PP_OK without a launch.  Reference consumer: Generator.batch's per-image
+ * lists (generator.py:96-97) of the CifDet generator (generator/cifdet.py:27-52).
+ */
+int pp_pack_det_records(const pp_det *d_dets, const int32_t *d_counts, const int32_t *d_status,
+                        int32_t n_img, int32_t det_capacity, pp_det *out, int64_t out_capacity,
+                        int32_t *out_counts, int32_t *out_status, void *stream);
+
+/*
  * The same hand-over with COMPACT records (the wire format of the host fetch and the
  * multi-GPU gather): a pp_ann cut to K keypoints, pp_packed_record_size(K, C, flags) bytes
  * (a multiple of 16), little-endian:

@@ -2,9 +2,10 @@
 // one caller buffer (Generator.batch's list of per-image Annotation lists, generator.py:96-97,
 // flattened); the destination may be mapped pinned host memory (zero-copy).
 //   pack_records_kernel / pp_pack_records   whole pp_ann records
+//   pack_det_records_kernel / pp_pack_det_records   whole pp_det records, counts and status
 //   pack_compact_kernel / pp_pack_compact   compact records (PackLayout / pack_layout,
 //                                           packed_word; pp_packed_record_size gives the size)
-// One workgroup per image in both.
+// One workgroup per image in all three.
 #include "pack_common.hpp"
 
 namespace pp {
@@ -26,6 +27,29 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const pp_ann *__restr
     static_assert(sizeof(pp_ann) % 8 == 0, "pp_ann is copied in 8-byte words");
     const uint64_t *src = reinterpret_cast<const uint64_t *>(anns + (int64_t)img * cap);
     store_words(reinterpret_cast<uint64_t *>(out + off), src, fit * kWords, (int)threadIdx.x, 256);
+}
+
+// The same for the detection decoder's records, with the decode's status words beside the
+// counts: a pp_det is two 16-byte chunks, thread t copies chunks t, t + 256, ... of the
+// image's records (16-byte loads and stores; rows and destination are 16-byte aligned, so
+// every chunk is).  Reads stop at the row's capacity whatever the count says.
+__global__ __launch_bounds__(256) void pack_det_records_kernel(
+    const pp_det *__restrict__ dets, const int *__restrict__ counts,
+    const int *__restrict__ status, int n, int cap, pp_det *out, int64_t out_cap, int *out_counts,
+    int *out_status) {
+    __shared__ int s_off;
+    const int img = blockIdx.x;
+    const int64_t off = packed_offset(counts, img, s_off);
+    const int cnt = counts[img];
+    if (threadIdx.x == 0) {
+        out_counts[img] = cnt;
+        if (out_status) out_status[img] = status[img];
+    }
+    const int64_t fit = min((int64_t)min(cnt, cap), max((int64_t)0, out_cap - off));
+    static_assert(sizeof(pp_det) == 32, "pp_det is copied as two 16-byte chunks");
+    const uint4 *src = reinterpret_cast<const uint4 *>(dets + (int64_t)img * cap);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + off);
+    for (int64_t c = threadIdx.x; c < 2 * fit; c += 256) dst[c] = src[c];
 }
 
 // -------------------------------------------------------------------------------------
@@ -199,6 +223,30 @@ int pp_pack_records(const pp_ann *d_anns, const int32_t *d_counts, int32_t n_img
                        (hipStream_t)stream, d_anns, d_counts, n_img, ann_capacity,
                        (pp_ann *)dst[0], out_capacity, (int *)dst[1]);
     return check_launch("pp_pack_records");
+}
+
+int pp_pack_det_records(const pp_det *d_dets, const int32_t *d_counts, const int32_t *d_status,
+                        int32_t n_img, int32_t det_capacity, pp_det *out, int64_t out_capacity,
+                        int32_t *out_counts, int32_t *out_status, void *stream) {
+    if (!d_dets || !d_counts || !out || !out_counts)
+        return fail(PP_EINVAL, "pp_pack_det_records: NULL argument");
+    if (!d_status != !out_status)
+        return fail(PP_EINVAL, "pp_pack_det_records: d_status and out_status go together");
+    if (n_img < 0 || det_capacity <= 0 || out_capacity < 0)
+        return fail(PP_ESHAPE, "pp_pack_det_records: bad shape");
+    if (reinterpret_cast<uintptr_t>(d_dets) & 15)
+        return fail(PP_EINVAL, "pp_pack_det_records: records not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15)
+        return fail(PP_EINVAL, "pp_pack_det_records: destination not 16-byte aligned");
+    if (n_img == 0) return PP_OK;
+    void *dst[3] = {out, out_counts, out_status};  // out_status is optional
+    if (const int rd = map_destinations("pp_pack_det_records", dst, 3)) return rd;
+    if (reinterpret_cast<uintptr_t>(dst[0]) & 15)  // the mapped address, should it differ
+        return fail(PP_EINVAL, "pp_pack_det_records: destination not 16-byte aligned");
+    hipLaunchKernelGGL(pack_det_records_kernel, dim3((unsigned)n_img), dim3(256), 0,
+                       (hipStream_t)stream, d_dets, d_counts, d_status, n_img, det_capacity,
+                       (pp_det *)dst[0], out_capacity, (int *)dst[1], (int *)dst[2]);
+    return check_launch("pp_pack_det_records");
 }
 
 int64_t pp_packed_record_size(int32_t K, int32_t C, uint32_t flags) {

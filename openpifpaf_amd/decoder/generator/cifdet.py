@@ -15,7 +15,7 @@ from ... import _device
 from ..._abi import DET_DTYPE, DetNms, check_seed_mask, make_config, scale_list
 from ..._lib import PPError, call, load
 from ...annotation import AnnotationDet
-from ...engine import RaggedDetFields
+from ...engine import DetEngine, RaggedDetFields
 from .. import nms
 from ..cif_hr import CifHr
 from ..cif_seeds import CifSeeds
@@ -40,6 +40,8 @@ class CifDet(Generator):
         self.field_config = field_config
         self.categories = categories
         self._ws = None
+        # the persistent buffers and the record hand-over of decode_records and everything above
+        self.engine = DetEngine()
 
     def single_head(self):
         """One detection head without a min scale: pp_cifdet_decode; anything else (several
@@ -61,17 +63,22 @@ class CifDet(Generator):
                            seed_score_scale=CifSeeds.score_scale, stride=int(stride),
                            cif_neighbors=CifHr.neighbors, seed_mask=self.field_config.seed_mask)
 
+    def nms_config(self):
+        return det_nms_config()
+
+    def decode_async(self, det_batch, cap=None):
+        """decode_records enqueued on the current stream (one decode, one record pack into
+        pinned host memory, no read-back): an engine.PendingDetRecords, whose result() waits
+        and gives decode_records' (records, offsets) and whose annotations() gives
+        decode_batch's lists.  det_batch stays unchanged until then."""
+        return self.engine.decode_async(self, det_batch, cap)
+
     def decode_records(self, det_batch, cap=None):
         """det_batch (B, K, 7, H, W), or with several heads / min scales the list of the
         FieldConfig's heads (each (B, K, 7, H_m, W_m), cif_indices order) -> (pp_det
-        records, per-image offsets)."""
-        out, counts = self.decode_device(det_batch, cap)
-        b = len(counts)
-        counts = counts.cpu().numpy().astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
-        host = out.cpu().numpy()
-        recs = np.concatenate([host[i, :counts[i]].reshape(-1) for i in range(b)])
-        return np.frombuffer(recs.tobytes(), dtype=DET_DTYPE), offsets
+        records, per-image offsets).  One decode, one pack and one synchronisation in the
+        engine's buffers (engine.DetEngine); the records lie in pinned host memory."""
+        return self.decode_async(det_batch, cap).result()
 
     def coco_batch(self, det_batch, metas, **params):
         """decode_records' input and one meta dict per image (with 'image_id') -> the batch's
@@ -90,9 +97,8 @@ class CifDet(Generator):
         heads = self.head_fields(heads)
         return self.coco_batch(heads[0] if self.single_head() else heads, metas, **params)
 
-    def decode_device(self, det_batch, cap=None):
-        """decode_records up to the device records: ((B, cap, record bytes) uint8, (B) int32
-        counts), complete (the capacity doubles until no image overflows)."""
+    def device_heads(self, det_batch):
+        """decode_records' input as the checked list of the heads' device tensors."""
         heads = [_device.to_device(t) for t in
                  (det_batch if isinstance(det_batch, (list, tuple)) else [det_batch])]
         for det in heads:
@@ -101,10 +107,16 @@ class CifDet(Generator):
         if len(heads) != len(self.field_config.cif_indices):
             raise ValueError('expected {} CifDet heads, got {}'.format(
                 len(self.field_config.cif_indices), len(heads)))
+        if any(t.shape[:3] != heads[0].shape[:3] for t in heads):
+            raise ValueError('CifDet heads differ in batch or field count')
+        return heads
+
+    def decode_device(self, det_batch, cap=None):
+        """decode_records up to the device records: ((B, cap, record bytes) uint8, (B) int32
+        counts), complete (the capacity doubles until no image overflows)."""
+        heads = self.device_heads(det_batch)
         det = heads[0]
         b, k, _, h, w = det.shape
-        if any(t.shape[:3] != det.shape[:3] for t in heads):
-            raise ValueError('CifDet heads differ in batch or field count')
         cfg = self.config()
         z = det_nms_config()
         cells = sum(t.shape[3] * t.shape[4] for t in heads)
@@ -195,12 +207,13 @@ class CifDet(Generator):
     def decode_ragged_records(self, fields_list, cap=None, **kw):
         """decode_ragged up to the records: (pp_det records of all images, per-image
         offsets); pp_det.image is the image's position in the batch."""
-        out, counts = self.decode_ragged_device(self._ragged(fields_list, kw), cap)
-        counts = counts.cpu().numpy().astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
-        host = out.cpu().numpy()
-        recs = np.concatenate([host[i, :counts[i]].reshape(-1) for i in range(len(counts))])
-        return np.frombuffer(recs.tobytes(), dtype=DET_DTYPE), offsets
+        return self.decode_ragged_async(fields_list, cap, **kw).result()
+
+    def decode_ragged_async(self, fields_list, cap=None, **kw):
+        """decode_ragged_records enqueued on the current stream, as decode_async: an
+        engine.PendingDetRecords (result(): the records and offsets; annotations():
+        decode_ragged's lists)."""
+        return self.engine.decode_async(self, self._ragged(fields_list, kw), cap)
 
     def decode_ragged(self, fields_list, **kw):
         """One entry per image, each image's head outputs [det (K, 7, h_i, w_i), ...] at its

@@ -6,6 +6,7 @@ Records come back as a NumPy structured array (openpifpaf_amd._abi.ANN_DTYPE) pa
 the whole batch plus per-image offsets; decoder/generator/cifcaf.py turns them into
 Annotation objects.
 """
+import collections
 import ctypes
 import logging
 
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _device
-from ._abi import (ANN_DTYPE, PACK_ALL, PP_ST_ANN_OVERFLOW, PP_ST_DEC_OVERFLOW,
+from ._abi import (ANN_DTYPE, DET_DTYPE, PACK_ALL, PP_ST_ANN_OVERFLOW, PP_ST_DEC_OVERFLOW,
                    PP_ST_NMS_OVERFLOW, packed_dtype, scale_list, skeleton_array)
 from ._lib import PPError, call, load
 
@@ -1142,6 +1143,271 @@ class DecodePipeline:
 
     def _note_counts(self, counts):
         self.density = float(counts.mean()) if len(counts) else 0.0
+
+
+# ---- the detection decoder's engine (decoder/generator/cifdet.py) ---------------------------
+class DetBuffers:
+    """Workspace + two output slots (records, counts, status) of one CifDet decode shape:
+    DecodeBuffers for the detection decoder.  `bound` is the capacity no image can exceed
+    (K * cells), where the overflow retry stops."""
+
+    def __init__(self, key, n, cap, size, bound, device):
+        self.key, self.n, self.cap, self.bound = key, n, cap, bound
+        self.ws = torch.empty(size, dtype=torch.uint8, device=device)
+        self._slots = [(torch.empty((n, cap, DET_DTYPE.itemsize), dtype=torch.uint8,
+                                    device=device),
+                        torch.zeros(n, dtype=torch.int32, device=device),
+                        torch.zeros(n, dtype=torch.int32, device=device)) for _ in range(2)]
+        self._cur = 0
+        self._free = [None, None]  # per slot: event after which its records were packed
+        self.decodes = [0, 0]  # per slot: decodes written into it so far
+        self.busy = None  # event behind the last decode / pack enqueued on these buffers
+        self.inputs = None  # (cifdet, device batch, config) of the last launch, for its retry
+
+    out = property(lambda self: self._slots[self._cur][0])
+    counts = property(lambda self: self._slots[self._cur][1])
+    status = property(lambda self: self._slots[self._cur][2])
+
+    def next_slot(self):
+        """DecodeBuffers.next_slot: the other slot, once its previous records have been
+        packed.  Counts the slot's decodes, so that a pending fetch can tell whether the slot
+        still holds its records."""
+        self._cur ^= 1
+        self.decodes[self._cur] += 1
+        if self._free[self._cur] is not None:
+            torch.cuda.current_stream().wait_event(self._free[self._cur])
+            self._free[self._cur] = None
+
+    def storage(self):
+        """data_ptr of the workspace and of each slot's records, counts and status."""
+        return (self.ws.data_ptr(),) + tuple(t.data_ptr() for s in self._slots for t in s)
+
+
+class DetEngine:
+    """The persistent state of one CifDet: per (entry point, batch shape, capacity) a
+    workspace and two output slots (DetBuffers), kept between calls, and the record
+    hand-over through pp_pack_det_records.  launch() enqueues one decode, fetch_async() its
+    pack into a pinned host block (records, counts and status: one synchronisation hands
+    over everything), PendingDetRecords.result() waits.  A call of a shape seen before
+    allocates nothing on the device.
+
+    A slot is not rewritten before the pack that reads it is done (DecodeBuffers.next_slot),
+    and a decode waits for whatever last used its workspace, on any stream, so decodes of one
+    engine may be enqueued on different streams (DetPipeline).  The detection decode uses no
+    library side stream: everything runs on the stream current at the call."""
+
+    KEYS = 4  # shapes kept; the least recently used goes first
+
+    def __init__(self):
+        self._bufs = collections.OrderedDict()
+        self.pack_cap = 0  # records the pinned block reserves: the largest batch seen, doubled
+
+    def buffers(self, key, n, cap, size, bound, device):
+        b = self._bufs.get(key)
+        if b is not None:
+            self._bufs.move_to_end(key)
+            return b
+        while len(self._bufs) >= self.KEYS:
+            _, old = self._bufs.popitem(last=False)
+            if old.busy is not None:  # its memory goes back to the allocator: work done first
+                old.busy.synchronize()
+        b = self._bufs[key] = DetBuffers(key, n, cap, size, bound, device)
+        return b
+
+    def storage(self):
+        """{buffer key: DetBuffers.storage()} of the shapes held."""
+        return {key: b.storage() for key, b in self._bufs.items()}
+
+    def launch(self, cifdet, batch, cap=None, config=None):
+        """Enqueue one decode on the current stream, no read-back; returns the DetBuffers,
+        whose current slot the decode writes.  `batch`: a (B, K, 7, H, W) tensor, the list of
+        the head tensors of a multi-head or min-scale FieldConfig, or a RaggedDetFields;
+        pp_cifdet_decode, pp_cifdet_decode_multi or pp_cifdet_decode_ragged as
+        CifDet.decode_device / decode_ragged_device choose.  `config`: the (pp_config,
+        pp_det_nms) of an earlier launch instead of the decoder classes' attributes as they
+        are now (the overflow retry decodes with what the first attempt read)."""
+        lib = load()
+        cfg, z = config or (cifdet.config(), cifdet.nms_config())
+        fc = cifdet.field_config
+        arr = pairs = None
+        if isinstance(batch, RaggedDetFields):
+            n, k, h, w = batch.n, batch.k, batch.h, batch.w
+            kind, shape, cells, dev = 'ragged', (h, w), h * w, batch.det.device
+            cap = cap or max(64, h * w)
+            size = lib.pp_cifdet_ragged_workspace_size(n, k, h, w, ctypes.byref(cfg), cap)
+        else:
+            heads = cifdet.device_heads(batch)
+            n, k, _, h, w = heads[0].shape
+            cells, dev = sum(t.shape[3] * t.shape[4] for t in heads), heads[0].device
+            cap = cap or max(64, h * w)
+            if cifdet.single_head():
+                kind, shape, batch = 'single', (h, w), heads[0]
+                size = lib.pp_cifdet_workspace_size(n, k, h, w, ctypes.byref(cfg), cap)
+            else:
+                arr = scale_list([(t.data_ptr(), t.shape[3], t.shape[4]) for t in heads], [],
+                                 fc.cif_strides, [], fc.cif_min_scales)
+                pairs = int(len(heads) == 10)  # CifHr.fill's 10-head layout (cif_hr.py:68-73)
+                kind, batch = 'multi', heads
+                shape = (pairs,) + tuple((s.H, s.W, s.stride, s.cif_min_scale) for s in arr)
+                size = lib.pp_cifdet_multi_workspace_size(arr, len(arr), pairs, n, k, cap)
+        b = self.buffers((kind, n, k, shape, cap, int(size), dev), n, cap, int(size), k * cells,
+                         dev)
+        if b.busy is not None:
+            torch.cuda.current_stream(dev).wait_event(b.busy)
+        b.next_slot()
+        out = (ctypes.byref(cfg), ctypes.byref(z), _device.ptr(None), _device.ptr(b.out), cap,
+               _device.ptr(b.counts), _device.ptr(b.status), _device.ptr(b.ws),
+               ctypes.c_size_t(b.ws.numel()), _device.stream())
+        if kind == 'ragged':
+            call('pp_cifdet_decode_ragged', _device.ptr(batch.det), n, k, h, w,
+                 _device.ptr(batch.extents),
+                 batch.extents_host.ctypes.data_as(ctypes.c_void_p), *out)
+        elif kind == 'multi':
+            call('pp_cifdet_decode_multi', arr, len(arr), pairs, n, k, *out)
+        else:
+            call('pp_cifdet_decode', _device.ptr(batch), n, k, h, w, *out)
+        b.busy = torch.cuda.Event()
+        b.busy.record()
+        b.inputs = (cifdet, batch, (cfg, z))
+        return b
+
+    def fetch_async(self, b, capacity=0, stream=None):
+        """Enqueue the record pack of the last decode into `b` and return a
+        PendingDetRecords: pp_pack_det_records writes the counts, the decode's status and the
+        records, image after image, straight into a pinned host block (zero-copy through its
+        mapped address).  The block is sized from the largest batch seen (`capacity` = records
+        to reserve at least); result() packs a batch that outgrew it again, or decodes it again
+        should the slot have been rewritten meanwhile (the second decode into `b` after this
+        one takes it).  On the current stream, behind the decode, or on `stream` after it."""
+        est = max(self.pack_cap, 16 * b.n, capacity)
+        p = self._pack(b, b._cur, b.inputs, est, stream)
+        b._free[b._cur] = b.busy = p.done_event
+        return p
+
+    def _pack(self, b, slot_i, inputs, est, stream=None):
+        n, slot = b.n, b._slots[slot_i]
+        head = -(-8 * n // 256) * 256  # counts (n int32), status (n int32), then the records
+        host = torch.empty(head + est * DET_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        cur = torch.cuda.current_stream(slot[0].device)
+        side = cur if stream is None else stream
+        if side != cur:
+            side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            base = host.data_ptr()
+            call('pp_pack_det_records', _device.ptr(slot[0]), _device.ptr(slot[1]),
+                 _device.ptr(slot[2]), n, b.cap, ctypes.c_void_p(base + head), est,
+                 ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * n), _device.stream())
+            done = torch.cuda.Event()
+            done.record()
+        return PendingDetRecords(self, b, slot_i, inputs, host, head, est, done)
+
+    def decode_async(self, cifdet, batch, cap=None, config=None):
+        """launch + fetch_async: one decode and one pack on the current stream."""
+        return self.fetch_async(self.launch(cifdet, batch, cap, config))
+
+
+class PendingDetRecords:
+    """A detection record fetch enqueued by DetEngine.fetch_async.  It keeps the decode's
+    inputs alive, because result() decodes again when an image overflowed the capacity: the
+    caller leaves them unchanged until result() returns."""
+
+    def __init__(self, eng, b, slot_i, inputs, host, head, est, done):
+        self._eng, self._b, self._slot_i, self._inputs = eng, b, slot_i, inputs
+        self._cifdet, self._decode = inputs[0], b.decodes[slot_i]
+        self._host, self._head, self._est, self._done = host, head, est, done
+        self._waited, self._result = False, None
+
+    def __del__(self):
+        # the pinned block goes back to torch's host cache when this object dies; the raw
+        # pack kernel must have finished writing it by then
+        if not self._waited and self._done is not None:
+            try:
+                self._done.synchronize()
+            except Exception:  # pylint: disable=broad-except
+                pass
+
+    @property
+    def done_event(self):
+        return self._done
+
+    def wait(self):
+        """Wait for the pack: (per-image counts int64, the decode's status words int32)."""
+        n = self._b.n
+        self._done.synchronize()
+        self._waited = True
+        words = self._host[:8 * n].numpy().view(np.int32)
+        return words[:n].astype(np.int64), words[n:]
+
+    def result(self):
+        """(DET_DTYPE records of all images, per-image offsets) of a complete decode: waits
+        for the pack; where an image overflowed, decodes again at doubled capacity (PPError
+        once the capacity is K * cells and still overflows, as CifDet.decode_device); packs
+        again into a larger block when the batch outgrew this one."""
+        if self._result is not None:
+            return self._result
+        counts, status = self.wait()
+        b, eng = self._b, self._eng
+        if (status & PP_ST_ANN_OVERFLOW).any():
+            if b.cap >= b.bound:
+                raise PPError('CifDet: detection capacity overflow')
+            cap = min(b.bound, 2 * b.cap)
+            LOG.info('detection capacity overflow, retrying with %d per image', cap)
+            cifdet, batch, config = self._inputs
+            again = eng.decode_async(cifdet, batch, cap, config)
+        else:
+            offsets = np.concatenate([[0], np.cumsum(counts)])
+            total = int(offsets[-1])
+            if total <= self._est:
+                size = total * DET_DTYPE.itemsize
+                recs = self._host[self._head:self._head + size].numpy().view(DET_DTYPE)
+                self._result = (recs, offsets)
+                self._inputs = None
+                return self._result
+            eng.pack_cap = max(eng.pack_cap, 2 * total)  # outgrew the block
+            if b.decodes[self._slot_i] == self._decode:  # the slot still holds the records
+                # pylint: disable=protected-access
+                again = eng._pack(b, self._slot_i, self._inputs, eng.pack_cap)
+                b._free[self._slot_i] = again.done_event  # its next decode waits for this too
+            else:  # rewritten by a later decode: once more from the inputs
+                cifdet, batch, config = self._inputs
+                again = eng.decode_async(cifdet, batch, b.cap, config)
+        self._result = again.result()
+        self._inputs = None
+        return self._result
+
+    def annotations(self):
+        """One list of AnnotationDet per image (CifDet.decode_batch's lists)."""
+        return self._cifdet.annotations_from_records(*self.result())
+
+
+class DetPipeline:
+    """Detection decodes of a sequence of batches, consecutive ones overlapped on the device:
+    batch i's decode and its pack run on stream i % 2 of the pipeline's own two streams, after
+    what the caller's current stream held at submit, so one batch's latency-bound select loop
+    (one wave per field) runs beside the next batch's bandwidth-bound CifHr map.  `depth`
+    engines (workspaces in flight, at least two) alternate; a decode waits for the pack that
+    last used its workspace and for the pack that last read its slot (DetEngine.launch).
+    The detection decode uses no library side stream, so a process has the current stream and
+    these two in use (HIP shares 4 hardware queues per process between streams).
+
+    submit() returns the batch's PendingDetRecords.  The current stream does not wait for the
+    decode; the inputs stay unchanged until the batch's result() has returned."""
+
+    def __init__(self, device=None, depth=2):
+        self.device = _device.require() if device is None else device
+        self.depth = max(2, depth)
+        self.engines = tuple(DetEngine() for _ in range(self.depth))
+        self.streams = tuple(torch.cuda.Stream(device=self.device) for _ in range(2))
+        self._i = 0
+
+    def submit(self, cifdet, batch, cap=None):
+        """Enqueue one batch (DetEngine.launch's `batch`) for `cifdet`."""
+        i = self._i
+        self._i += 1
+        stream = self.streams[i % 2]
+        stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(stream):
+            return self.engines[i % self.depth].decode_async(cifdet, batch, cap)
 
 
 _ENGINE = None

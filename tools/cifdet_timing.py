@@ -2,8 +2,9 @@
 
     python tools/cifdet_timing.py --baseline-lib PATH [--new-first] [--runs 21] [--images 256]
     python tools/cifdet_timing.py --ragged [--runs 21]
+    python tools/cifdet_timing.py --fetch [--baseline-package DIR] [--runs 21] [--batches 20]
 
-HIP events around each call on the current stream, 3 warm-ups first, the cases of a group in
+--baseline-lib and --ragged: HIP events around each call on the current stream, 3 warm-ups first, the cases of a group in
 alternation, median and min-max of --runs (>= 20).  One JSON line per case.  3 categories,
 CifHr.v_threshold 0.1, seed threshold 0.3 (planted, synthetic.det_planted) or 0.1 (uniform,
 synthetic.det_uniform).
@@ -20,13 +21,25 @@ before anything is timed.
               (workspace) of its own, so no route allocates a workspace
   ceiling     (c) one checked uniform decode_device of 256 images of 81x81
 and a last line with the ratios a / b and a / c.  The ragged route's records are compared with
-the per-image route's before anything is timed."""
+the per-image route's before anything is timed.
+
+--fetch: the user-facing call, CifDet.decode_records on the 256 images of 80x80 (decode, record
+hand-over to the host and every synchronisation the call makes).  The path under test is host
+work and PCIe, so the clock is wall time around the call (time.perf_counter, the device idle
+before it), not HIP events.  With --baseline-package DIR (a checkout of the commit to compare
+against, built: DIR/openpifpaf_amd with its own libpifpaf_amd.so) that package is loaded
+beside this one under another name and the two alternate, parent first and then new first;
+their records are compared before anything is timed.  Then, this build only: --batches
+batches through engine.DetPipeline (all submitted, then all read) against the same number of
+sequential decode_records calls, alternating, per batch."""
 import argparse
 import ctypes
+import importlib.util
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -176,10 +189,111 @@ def ragged_routes(args, info):
         torch.cuda.empty_cache()
 
 
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def run_group_wall(cases, runs, warmup=3):
+    """run_group on the wall clock; every case synchronises itself."""
+    for _ in range(warmup):
+        for fn in cases.values():
+            fn()
+    times = {name: [] for name in cases}
+    for _ in range(runs):
+        for name, fn in cases.items():
+            times[name].append(wall(fn))
+    return {name: (statistics.median(t), min(t), max(t)) for name, t in times.items()}
+
+
+def load_parent_package(directory):
+    """DIR/openpifpaf_amd as the package `openpifpaf_amd_parent` (its imports are relative,
+    and its _lib loads the library beside it)."""
+    path = os.path.join(os.path.abspath(directory), 'openpifpaf_amd')
+    spec = importlib.util.spec_from_file_location(
+        'openpifpaf_amd_parent', os.path.join(path, '__init__.py'),
+        submodule_search_locations=[path])
+    module = importlib.util.module_from_spec(spec)
+    sys.modules['openpifpaf_amd_parent'] = module
+    spec.loader.exec_module(module)
+    return importlib.import_module('openpifpaf_amd_parent.decoder')
+
+
+def fetch_routes(args, info):
+    from openpifpaf_amd.engine import DetPipeline  # pylint: disable=import-outside-toplevel
+    n = args.images
+    cats = ['c%d' % i for i in range(K)]
+    packages = {'new': decoder}
+    if args.baseline_package:
+        packages['parent'] = load_parent_package(args.baseline_package)
+    for kind in ('planted', 'uniform'):
+        for pkg in packages.values():
+            pkg.CifHr.v_threshold = 0.1
+            pkg.CifSeeds.threshold = SEED_THRESHOLD[kind]
+        det = _device.to_device(synthetic.det_batch(kind, n, H, W, n_categories=K))
+        cds = {name: pkg.CifDet(pkg.FieldConfig(), cats) for name, pkg in packages.items()}
+        recs, offsets = cds['new'].decode_records(det)
+        common = dict(info, kind=kind, images=n, detections=int(offsets[-1]),
+                      record_bytes=int(offsets[-1]) * DET_DTYPE.itemsize)
+        if 'parent' in cds:
+            old, old_offsets = cds['parent'].decode_records(det)
+            assert old_offsets.tolist() == offsets.tolist()
+            assert old.tobytes() == recs.tobytes()
+            for first in ('parent', 'new'):
+                order = [first] + [name for name in cds if name != first]
+                cases = {name: (lambda cd=cds[name]: cd.decode_records(det)) for name in order}
+                res = run_group_wall(cases, args.runs)
+                for case, (med, lo, hi) in res.items():
+                    print(json.dumps(dict(common, group='fetch', case=case, first=first,
+                                          median_ms=round(med, 4), min_ms=round(lo, 4),
+                                          max_ms=round(hi, 4))), flush=True)
+                print(json.dumps(dict(
+                    common, group='fetch', case='verdict', first=first,
+                    new_over_parent=round(res['new'][0] / res['parent'][0], 4),
+                    new_median_at_or_below_parent_range=bool(
+                        res['new'][0] <= res['parent'][1]))), flush=True)
+        # the pipeline against the sequential engine, this build only
+        cd, steps = cds['new'], args.batches
+        pipe, piped = DetPipeline(), decoder.CifDet(decoder.FieldConfig(), cats)
+
+        def sequential():
+            for _ in range(steps):
+                cd.decode_records(det)
+
+        def pipeline():
+            pending = [pipe.submit(piped, det) for _ in range(steps)]
+            return [p.result() for p in pending]
+
+        got = pipeline()
+        assert all(r.tobytes() == recs.tobytes() and o.tolist() == offsets.tolist()
+                   for r, o in got)
+        del got
+        res = run_group_wall({'sequential': sequential, 'pipeline': pipeline}, args.runs)
+        for case, (med, lo, hi) in res.items():
+            print(json.dumps(dict(common, group='pipeline', case=case, batches=steps,
+                                  median_ms_per_batch=round(med / steps, 4),
+                                  min_ms_per_batch=round(lo / steps, 4),
+                                  max_ms_per_batch=round(hi / steps, 4),
+                                  images_per_s=round(n * steps / med * 1e3, 1))), flush=True)
+        seq, pip = res['sequential'], res['pipeline']
+        print(json.dumps(dict(common, group='pipeline', case='verdict', batches=steps,
+                              pipeline_over_sequential=round(pip[0] / seq[0], 4),
+                              pipeline_median_below_sequential_range=bool(pip[0] < seq[1]))),
+              flush=True)
+        del det, cds, cd, pipe, piped
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--baseline-lib', default=None)
     ap.add_argument('--ragged', action='store_true')
+    ap.add_argument('--fetch', action='store_true')
+    ap.add_argument('--baseline-package', default=None,
+                    help='--fetch: a built checkout of the commit to compare against')
+    ap.add_argument('--batches', type=int, default=20)
     ap.add_argument('--new-first', action='store_true',
                     help='--baseline-lib: this build before the parent in every alternation')
     ap.add_argument('--runs', type=int, default=21)
@@ -187,8 +301,8 @@ def main():
     args = ap.parse_args()
     if args.runs < 20:
         ap.error('--runs must be at least 20')
-    if not args.baseline_lib and not args.ragged:
-        ap.error('nothing to time: give --baseline-lib PATH and / or --ragged')
+    if not args.baseline_lib and not args.ragged and not args.fetch:
+        ap.error('nothing to time: give --baseline-lib PATH, --ragged and / or --fetch')
     _device.require()
     info = {'device': torch.cuda.get_device_name(0), 'library': build.source_digest(),
             'runs': args.runs, 'warmup': 3, 'clock': 'events'}
@@ -196,6 +310,8 @@ def main():
         against_parent(args, dict(info, baseline_lib=os.path.basename(args.baseline_lib)))
     if args.ragged:
         ragged_routes(args, info)
+    if args.fetch:
+        fetch_routes(args, dict(info, clock='wall'))
 
 
 if __name__ == '__main__':
