@@ -6,24 +6,19 @@ batch (`decode_batch`), or for images of different field sizes as one batch
 (`decode_ragged`, `coco_ragged`; engine.RaggedDetFields), configured from the CifHr /
 CifSeeds / nms.Detection class attributes as the reference's decoder.configure() sets them.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from ... import _device
-from ..._abi import DET_DTYPE, DetNms, check_seed_mask, make_config, scale_list
-from ..._lib import PPError, call, load
+from ..._abi import DET_DTYPE, PP_ST_ANN_OVERFLOW, DetNms, check_seed_mask, make_config
+from ..._lib import PPError, call
 from ...annotation import AnnotationDet
-from ...engine import DetEngine, RaggedDetFields
+from ...engine import DetEngine, RaggedDetFields, det_call, det_tail
 from .. import nms
 from ..cif_hr import CifHr
 from ..cif_seeds import CifSeeds
 from ..field_config import FieldConfig
 from .generator import Generator
-
-PP_ST_ANN_OVERFLOW = 1
-
 
 def det_nms_config(cls=None):
     cls = cls or nms.Detection
@@ -81,7 +76,7 @@ class CifDet(Generator):
         return self.decode_async(det_batch, cap).result()
 
     def coco_batch(self, det_batch, metas, **params):
-        """decode_records' input and one meta dict per image (with 'image_id') -> the batch's
+        """decode_device's input and one meta dict per image (with 'image_id') -> the batch's
         eval_coco.CocoRecords of detections: EvalCoco.from_predictions
         (eval_coco.py:108-158) on the device behind the decode.  `params`: max_per_image."""
         from ...eval_coco import coco_records, metas_device  # pylint: disable=import-outside-toplevel
@@ -113,45 +108,25 @@ class CifDet(Generator):
 
     def decode_device(self, det_batch, cap=None):
         """decode_records up to the device records: ((B, cap, record bytes) uint8, (B) int32
-        counts), complete (the capacity doubles until no image overflows)."""
-        heads = self.device_heads(det_batch)
-        det = heads[0]
-        b, k, _, h, w = det.shape
-        cfg = self.config()
-        z = det_nms_config()
-        cells = sum(t.shape[3] * t.shape[4] for t in heads)
-        fc = self.field_config
-        multi = not self.single_head()
-        arr = scale_list([(t.data_ptr(), t.shape[3], t.shape[4]) for t in heads], [],
-                         fc.cif_strides, [], fc.cif_min_scales) if multi else None
-        pairs = int(len(heads) == 10)  # CifHr.fill's 10-head layout (cif_hr.py:68-73)
-        cap = cap or max(64, h * w)
+        counts), complete (the capacity doubles until no image overflows) and the caller's
+        own, not an engine slot.  A RaggedDetFields as `det_batch`: decode_ragged_device."""
+        d = det_call(self, det_batch)
+        cfg, z = self.config(), det_nms_config()
+        cap, bound = cap or d.cap, d.k * d.cells
         while True:
-            if multi:
-                size = int(load().pp_cifdet_multi_workspace_size(arr, len(arr), pairs, b, k, cap))
-            else:
-                size = int(load().pp_cifdet_workspace_size(b, k, h, w, ctypes.byref(cfg), cap))
-            if self._ws is None or self._ws.numel() < size:
-                self._ws = torch.empty(size, dtype=torch.uint8, device=det.device)
-            out = torch.empty((b, cap, DET_DTYPE.itemsize), dtype=torch.uint8, device=det.device)
-            counts = torch.empty(b, dtype=torch.int32, device=det.device)
-            status = torch.empty(b, dtype=torch.int32, device=det.device)
-            if multi:
-                call('pp_cifdet_decode_multi', arr, len(arr), pairs, b, k, ctypes.byref(cfg),
-                     ctypes.byref(z), _device.ptr(None), _device.ptr(out), cap,
-                     _device.ptr(counts), _device.ptr(status), _device.ptr(self._ws),
-                     ctypes.c_size_t(self._ws.numel()), _device.stream())
-            else:
-                call('pp_cifdet_decode', _device.ptr(det), b, k, h, w, ctypes.byref(cfg),
-                     ctypes.byref(z), _device.ptr(None), _device.ptr(out), cap,
-                     _device.ptr(counts), _device.ptr(status), _device.ptr(self._ws),
-                     ctypes.c_size_t(self._ws.numel()), _device.stream())
+            size = d.size(cfg, cap)
+            if self._ws is None or self._ws.numel() < size or self._ws.device != d.device:
+                self._ws = torch.empty(size, dtype=torch.uint8, device=d.device)
+            out = torch.empty((d.n, cap, DET_DTYPE.itemsize), dtype=torch.uint8, device=d.device)
+            counts = torch.empty(d.n, dtype=torch.int32, device=d.device)
+            status = torch.empty(d.n, dtype=torch.int32, device=d.device)
+            call(d.name, *d.lead, *det_tail(cfg, z, out, cap, counts, status, self._ws))
             st = status.cpu().numpy()
             if not (st & PP_ST_ANN_OVERFLOW).any():
                 break
-            if cap >= k * cells:
+            if cap >= bound:
                 raise PPError('CifDet: detection capacity overflow')
-            cap = min(k * cells, 2 * cap)
+            cap = min(bound, 2 * cap)
         return out, counts
 
     # -- ragged batches: images of different field sizes -----------------------------------
@@ -178,31 +153,7 @@ class CifDet(Generator):
     def decode_ragged_device(self, ragged, cap=None):
         """decode_device over a RaggedDetFields (pp_cifdet_decode_ragged), the workspace at the
         container's shape: ((n, cap, record bytes) uint8, (n) int32 counts), complete."""
-        n, k, h, w = ragged.n, ragged.k, ragged.h, ragged.w
-        cfg = self.config()
-        z = det_nms_config()
-        cap = cap or max(64, h * w)
-        dev = ragged.det.device
-        while True:
-            size = int(load().pp_cifdet_ragged_workspace_size(n, k, h, w, ctypes.byref(cfg), cap))
-            if self._ws is None or self._ws.numel() < size or self._ws.device != dev:
-                self._ws = torch.empty(size, dtype=torch.uint8, device=dev)
-            out = torch.empty((n, cap, DET_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            counts = torch.empty(n, dtype=torch.int32, device=dev)
-            status = torch.empty(n, dtype=torch.int32, device=dev)
-            call('pp_cifdet_decode_ragged', _device.ptr(ragged.det), n, k, h, w,
-                 _device.ptr(ragged.extents),
-                 ragged.extents_host.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cfg),
-                 ctypes.byref(z), _device.ptr(None), _device.ptr(out), cap, _device.ptr(counts),
-                 _device.ptr(status), _device.ptr(self._ws), ctypes.c_size_t(self._ws.numel()),
-                 _device.stream())
-            st = status.cpu().numpy()
-            if not (st & PP_ST_ANN_OVERFLOW).any():
-                break
-            if cap >= k * h * w:
-                raise PPError('CifDet: detection capacity overflow')
-            cap = min(k * h * w, 2 * cap)
-        return out, counts
+        return self.decode_device(ragged, cap)
 
     def decode_ragged_records(self, fields_list, cap=None, **kw):
         """decode_ragged up to the records: (pp_det records of all images, per-image
@@ -224,14 +175,10 @@ class CifDet(Generator):
 
     def coco_ragged(self, fields_list, metas, **params):
         """coco_batch for images of different field sizes (decode_ragged's `fields_list`)."""
-        from ...eval_coco import coco_records, metas_device  # pylint: disable=import-outside-toplevel
         ragged = self._ragged(fields_list, {k: params.pop(k) for k in ('group',) if k in params})
         if len(metas) != ragged.n:
             raise ValueError('{} metas for {} images'.format(len(metas), ragged.n))
-        out, counts = self.decode_ragged_device(ragged)
-        d_metas, d_ids, _ = metas_device(metas, 0)
-        return coco_records(out, counts, d_metas, d_ids, det=True,
-                            k=params.pop('n_keypoints', 17), **params)
+        return self.coco_batch(ragged, metas, **params)
 
     def annotations_from_records(self, recs, offsets):
         return [[AnnotationDet.from_record(r, self.categories)

@@ -23,6 +23,7 @@ from . import _device, transforms
 from ._abi import (COCO_DET_DTYPE, PP_COCO_EMPTY, PP_COCO_NAN, PP_ST_ANN_OVERFLOW,
                    PP_ST_DEC_OVERFLOW, PP_ST_NMS_OVERFLOW, CocoParams, coco_dtype)
 from ._lib import PPError, call, load
+from .engine.handover import PinnedBlock, offsets_of
 
 KEYS = ('category_id', 'score', 'keypoints', 'bbox', 'image_id')
 
@@ -120,42 +121,29 @@ class PendingCoco:
     """COCO records enqueued by `coco_records` / DecodeEngine.fetch_coco_async: a pinned
     block (counts, decode status, flags, then the records) the device writes zero-copy."""
 
-    def __init__(self, launch, host, head, est, done, n, k, det, stream):
-        self._launch, self._host, self._head, self._est = launch, host, head, est
-        self._done, self._n, self._k, self._det, self._stream = done, n, k, det, stream
-        self._waited = False
+    def __init__(self, launch, block, k, det, stream):
+        self._launch, self._block, self._k, self._det, self._stream = launch, block, k, det, stream
         self.dtype = COCO_DET_DTYPE if det else coco_dtype(k)
-
-    def __del__(self):
-        if not self._waited and self._done is not None:
-            try:
-                self._done.synchronize()
-            except Exception:  # pylint: disable=broad-except
-                pass
 
     @property
     def done_event(self):
-        return self._done
+        return self._block.done
 
     def result(self):
         """The batch's CocoRecords (waits; packs again when the batch outgrew the block)."""
-        n = self._n
-        self._done.synchronize()
-        self._waited = True
-        status = self._host[4 * n:8 * n].numpy().view(np.int32)
+        block = self._block
+        block.wait()
+        status = block.status()
         bad = status & (PP_ST_ANN_OVERFLOW | PP_ST_DEC_OVERFLOW | PP_ST_NMS_OVERFLOW)
         if bad.any():
             raise PPError('decode status flags set (records truncated): {}'.format(
                 status[bad != 0][:8].tolist()))
-        counts = self._host[:4 * n].numpy().view(np.int32).astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(counts)])
+        offsets = offsets_of(block.counts())
         total = int(offsets[-1])
-        if total > self._est:
+        if total > block.est:
             return self._launch(2 * total, self._stream).result()
-        width = self.dtype.itemsize
-        recs = self._host[self._head:self._head + total * width].numpy().view(self.dtype)
-        flags = self._host[8 * n:12 * n].numpy().view(np.int32)
-        return CocoRecords(recs, offsets, flags, self._k, self._det)
+        return CocoRecords(block.records(total, self.dtype), offsets, block.flags(), self._k,
+                           self._det)
 
 
 def coco_records_async(recs, counts, metas, image_ids, *, k=17, hswap=None, small_threshold=0.0,
@@ -171,18 +159,16 @@ def coco_records_async(recs, counts, metas, image_ids, *, k=17, hswap=None, smal
     n, cap = recs.shape[0], recs.shape[1]
     params = CocoParams(float(small_threshold), int(max_per_image), int(category_id))
     width = (COCO_DET_DTYPE if det else coco_dtype(k)).itemsize
-    head = -(-12 * n // 256) * 256
     ws_size = max(256, int(load().pp_coco_workspace_size(n)))
 
     def launch(est, side):
-        host = torch.empty(head + est * width, dtype=torch.uint8, pin_memory=True)
-        host[4 * n:8 * n].zero_()
+        block = PinnedBlock(n, 3, est, width)  # counts, the decode's status, flags, records
+        block.word_bytes(1).zero_()
         with torch.cuda.stream(side):
             # the per-image counts between the two launches; one per call, so calls on
             # different streams do not share it
             ws = torch.empty(ws_size, dtype=torch.uint8, device=recs.device)
-            tail = (ctypes.byref(params), ctypes.c_void_p(host.data_ptr() + head), est,
-                    ctypes.c_void_p(host.data_ptr()), ctypes.c_void_p(host.data_ptr() + 8 * n),
+            tail = (ctypes.byref(params), block.records_ptr(), est, block.ptr(0), block.ptr(2),
                     _device.ptr(ws), _device.stream())
             if det:
                 call('pp_coco_dets', _device.ptr(recs), _device.ptr(counts), n, cap,
@@ -191,13 +177,13 @@ def coco_records_async(recs, counts, metas, image_ids, *, k=17, hswap=None, smal
                 call('pp_coco_keypoints', _device.ptr(recs), _device.ptr(counts), n, cap, k,
                      _device.ptr(metas), _device.ptr(image_ids), _device.ptr(hswap), *tail)
             if status is not None:
-                host[4 * n:8 * n].copy_(status.view(torch.uint8), non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
+                block.word_bytes(1).copy_(status.view(torch.uint8), non_blocking=True)
+            block.done = torch.cuda.Event()
+            block.done.record()
             for t in (recs, counts, metas, image_ids, hswap, status):
                 if t is not None:
                     t.record_stream(side)
-        return PendingCoco(launch, host, head, est, done, n, k, det, side)
+        return PendingCoco(launch, block, k, det, side)
 
     est = max(int(capacity), 1) if capacity else max(1, n * min(int(max_per_image), cap))
     return launch(est, stream or torch.cuda.current_stream(recs.device))
@@ -236,7 +222,7 @@ def coco_records_cpu(recs, counts, metas, image_ids, *, k=17, hswap=None, small_
     else:
         call('pp_coco_keypoints_cpu', vp(recs), vp(counts), n, cap, k, vp(metas), vp(image_ids),
              vp(hswap), *tail)
-    offsets = np.concatenate([[0], np.cumsum(out_counts.astype(np.int64))])
+    offsets = offsets_of(out_counts)
     total = min(int(offsets[-1]), est)
     return CocoRecords(out[:total * dtype.itemsize].view(dtype), offsets, flags, k, det)
 

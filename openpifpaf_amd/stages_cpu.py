@@ -17,6 +17,7 @@ import numpy as np
 
 from ._abi import ANN_DTYPE, PP_ST_ANN_OVERFLOW, PP_ST_DEC_OVERFLOW, SEED_DTYPE
 from ._lib import PPError, call
+from .engine import default_ann_capacity, offsets_of
 
 
 def _f32(a, ndim, what):
@@ -134,7 +135,7 @@ def decode_batch(cif, caf, skeleton, cfg, *, n_threads=0, cap=None):
     sk = np.ascontiguousarray(skeleton, dtype=np.int32).reshape(-1, 2)
     if len(sk) != c:
         raise ValueError('skeleton has {} pairs for {} CAF fields'.format(len(sk), c))
-    cap = cap or int(min(8192, max(128, (h * w) // 8)))  # engine.default_ann_capacity
+    cap = cap or default_ann_capacity(h, w)
     while True:
         anns = np.zeros((max(1, n), cap), ANN_DTYPE)
         counts = np.zeros(max(1, n), np.int32)
@@ -147,7 +148,7 @@ def decode_batch(cif, caf, skeleton, cfg, *, n_threads=0, cap=None):
         cap *= 2
     if (status[:n] & PP_ST_DEC_OVERFLOW).any():
         raise PPError('decoding/frontier order exceeded the record capacity')
-    offsets = np.concatenate([[0], np.cumsum(counts[:n])]).astype(np.int64)
+    offsets = offsets_of(counts[:n])
     recs = np.concatenate([anns[i, :counts[i]] for i in range(n)]) if n else \
         np.zeros(0, ANN_DTYPE)
     return recs, offsets
@@ -189,7 +190,7 @@ def decode_ragged(cifs, cafs, skeleton, cfg, *, n_threads=0, cap=None):
     sk = np.ascontiguousarray(skeleton, dtype=np.int32).reshape(-1, 2)
     if len(sk) != c:
         raise ValueError('skeleton has {} pairs for {} CAF fields'.format(len(sk), c))
-    cap = cap or int(min(8192, max(128, (h * w) // 8)))  # engine.default_ann_capacity
+    cap = cap or default_ann_capacity(h, w)
     while True:
         anns = np.zeros((n, cap), ANN_DTYPE)
         counts = np.zeros(n, np.int32)
@@ -202,5 +203,5 @@ def decode_ragged(cifs, cafs, skeleton, cfg, *, n_threads=0, cap=None):
         cap *= 2
     if (status & PP_ST_DEC_OVERFLOW).any():
         raise PPError('decoding/frontier order exceeded the record capacity')
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    offsets = offsets_of(counts)
     return np.concatenate([anns[i, :counts[i]] for i in range(n)]), offsets

@@ -277,7 +277,7 @@ def test_cifdet_decode_ragged_from_channels_last_conv(dec, dtype_name):  # noqa:
     cd = _cifdet(dec, 'uniform')
     planar = engine.RaggedDetFields.from_conv(convs, det.rd.K, quad=1)
     last = engine.RaggedDetFields.from_conv([_nhwc(c) for c in convs], det.rd.K, quad=1)
-    assert last._ingest.interleaved and not planar._ingest.interleaved  # pylint: disable=protected-access
+    assert last._ingests[0].interleaved and not planar._ingests[0].interleaved  # pylint: disable=protected-access
     assert _bytes(last.det) == _bytes(planar.det)
     assert last.extents.cpu().numpy().tolist() == planar.extents_host.tolist()
     collected = heads.RaggedDetCollector(det.rd.K, quad=1)(([_nhwc(c) for c in convs],))

@@ -14,10 +14,9 @@ def test_pipeline_matches_engine_decode(b_first, split, monkeypatch):
     """Every placement of the force-complete sets (None: the density rule, which switches
     between lazy and first across these batches), the tail in one call or two."""
     import torch
-    from openpifpaf_amd import engine
-    from openpifpaf_amd.engine import DecodeEngine, DecodePipeline
-    monkeypatch.setattr(engine, '_B_FIRST', b_first)
-    monkeypatch.setattr(engine, '_SPLIT_TAIL', split)
+    from openpifpaf_amd.engine import DecodeEngine, DecodePipeline, pose
+    monkeypatch.setattr(pose, '_B_FIRST', b_first)
+    monkeypatch.setattr(pose, '_SPLIT_TAIL', split)
     skel = constants.COCO_PERSON_SKELETON
     cfg = make_config(**EVAL_CONFIG)
     compact = (17, len(skel), PACK_ALL)

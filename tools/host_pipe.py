@@ -44,7 +44,7 @@ torch.cuda.synchronize()
 
 
 # host time inside the library calls and the record-pack setup, per step
-from openpifpaf_amd import engine as _engine  # noqa: E402
+from openpifpaf_amd.engine import pose as _engine  # noqa: E402
 acc = {}
 
 
