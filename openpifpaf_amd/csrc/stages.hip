@@ -1074,6 +1074,11 @@ constexpr int kStashA = 256;      // kept columns per direction (set A stash): 2
 constexpr int kCandA = 1024;
 constexpr int kConfU = 16;
 constexpr int kStashCells = kSetBIdx16Max; // cells of all heads (set B stash: u16 bucket per direction)
+// Set B with the stash, ONE_ROUND: cells per thread whose five loads (confidence, source rows
+// 1, 2, 5, 6) are in flight together.  13 * 512 = 6656 cells in one round; 16 (the whole 8192)
+// would need 80 registers for the loads alone and the kernel must stay within 96 to run two
+// waves per SIMD beside the seed loop's.
+constexpr int kUB = 13;
 constexpr uint16_t kNoBucket = 0xFFFF;
 
 struct StashCol {
@@ -1083,7 +1088,7 @@ struct StashCol {
 
 // `ext` (hr_dims): NULL, or the images' own field sizes (caf_bucketed_ragged_kernel; set A
 // only: the index-only sets look nothing up in the map).
-template <bool INDEX_ONLY, bool STASH>
+template <bool INDEX_ONLY, bool STASH, bool ONE_ROUND = false>
 __device__ __forceinline__ void caf_bucketed_body(const CafBArgs &a, const int32_t *ext) {
     constexpr int NT = STASH && INDEX_ONLY ? 512 : 256;
     constexpr int NW = NT / 64;
@@ -1257,7 +1262,54 @@ __device__ __forceinline__ void caf_bucketed_body(const CafBArgs &a, const int32
     };
 
     bool listed = false;
-    if (kList && a.h.n_caf == 1) {
+    if constexpr (PK && ONE_ROUND) {
+        // Set B: the confidence and the four source rows of all of a thread's cells are
+        // loaded together, whether the cell passes or not (on real fields nearly all do):
+        // a field of up to NT * kUB cells costs one memory round trip.
+        for (int m = 0; m < a.h.n_caf; m++) {
+            const int hw = a.h.aH[m] * a.h.aW[m];
+            const float stride = (float)a.h.astride[m];
+            const float *p = a.h.caf[m] + fld * 9 * hw;
+            const int coff = (int)a.h.caf_off[m];
+            const bool on_min = (a.h.dmin_on >> m) & 1u, on_max = (a.h.dmax_on >> m) & 1u;
+            for (int base = 0; base < hw; base += NT * kUB) {
+                float c[kUB], x1[kUB], y1[kUB], x2[kUB], y2[kUB];
+#pragma unroll
+                for (int k = 0; k < kUB; k++) {
+                    const int cell = base + k * NT + (int)threadIdx.x;
+                    c[k] = NAN;  // NaN: never > score_th
+                    x1[k] = y1[k] = x2[k] = y2[k] = 0.0f;
+                    if (cell < hw) {
+                        c[k] = p[cell];
+                        x1[k] = p[1 * hw + cell];
+                        y1[k] = p[2 * hw + cell];
+                        x2[k] = p[5 * hw + cell];
+                        y2[k] = p[6 * hw + cell];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kUB; k++) {
+                    const int cell = base + k * NT + (int)threadIdx.x;
+                    bool keep = c[k] > a.th;  // mask = nine[0] > score_th
+                    if (keep && (on_min || on_max)) {  // caf_scored.py:46-56, raw vectors
+                        const float dx = x1[k] - x2[k], dy = y1[k] - y2[k];
+                        const float dist = sqrtf(dx * dx + dy * dy);
+                        if ((on_min && !(dist > a.h.dmin_th[m])) || (on_max && !(dist < a.h.dmax_th[m])))
+                            keep = false;
+                    }
+                    // source positions only: backward (x2, y2), forward (x1, y1)
+                    const int bkb = keep && need_b ? caf_bucket(x2[k] * stride, y2[k] * stride, a.bw, a.bh, a.inv_e) : -1;
+                    const int bkf = keep && need_f ? caf_bucket(x1[k] * stride, y1[k] * stride, a.bw, a.bh, a.inv_e) : -1;
+                    if (bkb >= 0) h_add(0, bkb);
+                    if (bkf >= 0) h_add(1, bkf);
+                    if (cell < hw) {
+                        stash_b[coff + cell] = bkb >= 0 ? (uint16_t)bkb : kNoBucket;
+                        stash_b[scell + coff + cell] = bkf >= 0 ? (uint16_t)bkf : kNoBucket;
+                    }
+                }
+            }
+        }
+    } else if (kList && a.h.n_caf == 1) {
         // list the cells above the threshold (confidence plane only)
         const int hw = a.h.aH[0] * a.h.aW[0];
         const float *p = a.h.caf[0] + fld * 9 * hw;
@@ -1340,7 +1392,7 @@ __device__ __forceinline__ void caf_bucketed_body(const CafBArgs &a, const int32
 #pragma unroll
             for (int k = 0; k < kU; k++) account(B, k, cells[k], hw, coff);
         }
-    } else {
+    } else if constexpr (!(PK && ONE_ROUND)) {
     for (int m = 0; m < a.h.n_caf; m++) {
         const int hw = a.h.aH[m] * a.h.aW[m];
         const float stride = (float)a.h.astride[m];
@@ -1484,9 +1536,9 @@ __device__ __forceinline__ void caf_bucketed_body(const CafBArgs &a, const int32
     }
 }
 
-template <bool INDEX_ONLY, bool STASH>
+template <bool INDEX_ONLY, bool STASH, bool ONE_ROUND = false>
 __global__ __launch_bounds__(STASH && INDEX_ONLY ? 512 : 256) void caf_bucketed_kernel(CafBArgs a) {
-    caf_bucketed_body<INDEX_ONLY, STASH>(a, nullptr);
+    caf_bucketed_body<INDEX_ONLY, STASH, ONE_ROUND>(a, nullptr);
 }
 
 __global__ __launch_bounds__(256) void caf_bucketed_ragged_kernel(CafBArgs a, const int32_t *ext) {
@@ -1649,7 +1701,13 @@ int launch_caf_bucketed(const Heads &h, const HrMap &hr, int n_img, int K, int C
         a.j2[i] = skeleton[2 * i + 1] - 1;
     }
     const dim3 grid((unsigned)((int64_t)n_img * C));
-    if (index_only && a.col_cap <= kStashCells)
+    // gated sets follow the seed loop and share their CUs with the next batch's, one workgroup
+    // per CU: the one-round form.  Ungated (early) sets have the CUs' registers to themselves,
+    // where the two-batch form's 70 VGPRs hold three workgroups per CU and the other's 90 two.
+    if (index_only && a.col_cap <= kStashCells && gate)
+        hipLaunchKernelGGL((caf_bucketed_kernel<true, true, true>), grid, dim3(512),
+                           (size_t)(2 * a.col_cap * sizeof(uint16_t)), s, a);
+    else if (index_only && a.col_cap <= kStashCells)
         hipLaunchKernelGGL((caf_bucketed_kernel<true, true>), grid, dim3(512),
                            (size_t)(2 * a.col_cap * sizeof(uint16_t)), s, a);
     else if (index_only)
