@@ -1234,6 +1234,56 @@ int pp_decode_ragged_cpu(const float *cif, const float *caf, int32_t n_img, int3
                          const pp_config *cfg, pp_ann *anns, int32_t ann_capacity,
                          int32_t *counts, int32_t *status, int32_t n_threads);
 
+/*
+ * Eval preprocessing (eval_coco.py:350-389 preprocess_factory without its options:
+ * RescaleAbsolute scale.py:113-134, CenterPad / CenterPadTight pad.py:12-111, EVAL_TRANSFORM
+ * transforms/__init__.py:20-27) of a batch of uint8 RGB images of different sizes in one launch.
+ *
+ * d_src holds the packed source images, each (h, w, 3) interleaved as PIL / np.asarray give
+ * them.  descs is a HOST table of n_img descriptors: it is checked on the host, extended by
+ * the zoom factors and the per-image first workgroup (a prefix sum) and staged into d_tables
+ * (pp_preprocess_tables_size(n_img) bytes, 8-byte aligned) beside the value table below, so
+ * the kernel reads its descriptors from the device.  Image i is resized to (th, tw) exactly
+ * as scipy.ndimage.zoom(im, (th / h, tw / w, 1), order=1) resizes uint8 (float64, every
+ * operation in scipy's order, no contraction; where the last coordinate rounds above h - 1
+ * or w - 1 the last row or column is 0, scipy's constant mode), pasted at (top, left) into an
+ * (H, W) output filled with `fill`, and every pixel mapped through
+ * ((float)u8 / 255.0f - mean[c]) / std[c], each one IEEE float32 operation, looked up in a
+ * 3 x 256 table the host computes (the device divides nothing).
+ *   dtype  PP_PRE_F32 / PP_PRE_F16 / PP_PRE_BF16: the float32 value, or its round-to-nearest-
+ *          even float16 / bfloat16; PP_PRE_U8: the padded uint8 image itself, always (H, W, 3)
+ *          (the image the reference holds before ToTensor; mean and std unused but checked)
+ *   layout PP_PRE_PLANAR (3, H, W) or PP_PRE_CHANNELS_LAST (H, W, 3) at out_offset
+ * src_offset counts bytes, out_offset and out_elems elements of the output type.
+ * PP_ESHAPE: n_img < 0, a source or target edge < 2, a source image beyond 2^31 - 1 bytes,
+ * H or W <= 0 (or H * W beyond 2^29), a
+ * target that does not fit its output with the given pad, a source image or an output region
+ * beyond its buffer.  PP_EINVAL: an unknown dtype or layout, a NULL pointer with n_img > 0, a
+ * std entry that is 0 or not finite, an output pointer not aligned to its type, a misaligned
+ * d_tables.  PP_ENOMEM: tables_bytes too small.  n_img == 0 succeeds and launches nothing.
+ * pp_preprocess_images_cpu is the host twin on host pointers (same checks, same per-pixel
+ * code: bit-identical outputs).
+ */
+enum { PP_PRE_F32 = 0, PP_PRE_F16 = 1, PP_PRE_BF16 = 2, PP_PRE_U8 = 3 };
+enum { PP_PRE_PLANAR = 0, PP_PRE_CHANNELS_LAST = 1 };
+typedef struct pp_image_desc {
+    int64_t src_offset;   /* first byte of the source image in the source buffer     */
+    int64_t out_offset;   /* first element of the image's output region              */
+    int32_t h, w;         /* source size                                              */
+    int32_t th, tw;       /* size after the rescale (th == h, tw == w: no rescale)    */
+    int32_t left, top;    /* pad before the rescaled image                            */
+    int32_t H, W;         /* output size                                              */
+} pp_image_desc;
+size_t pp_preprocess_tables_size(int32_t n_img);
+int pp_preprocess_images(const uint8_t *d_src, int64_t src_bytes, const pp_image_desc *descs,
+                         int32_t n_img, void *d_out, int64_t out_elems, int32_t dtype,
+                         int32_t layout, const float *mean, const float *std,
+                         const uint8_t *fill, void *d_tables, size_t tables_bytes, void *stream);
+int pp_preprocess_images_cpu(const uint8_t *src, int64_t src_bytes, const pp_image_desc *descs,
+                             int32_t n_img, void *out, int64_t out_elems, int32_t dtype,
+                             int32_t layout, const float *mean, const float *std,
+                             const uint8_t *fill);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,23 @@ CONV_HEAD_DTYPE = np.dtype([('d_container', '<u8'), ('layout', '<i4'), ('n_field
                             ('src_field', 'u1', (64,))])
 
 
+class ImageDesc(ctypes.Structure):
+    """pp_image_desc: one image of pp_preprocess_images."""
+    _fields_ = [('src_offset', ctypes.c_int64), ('out_offset', ctypes.c_int64),
+                ('h', ctypes.c_int32), ('w', ctypes.c_int32), ('th', ctypes.c_int32),
+                ('tw', ctypes.c_int32), ('left', ctypes.c_int32), ('top', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32)]
+
+
+IMAGE_DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('out_offset', '<i8'), ('h', '<i4'),
+                             ('w', '<i4'), ('th', '<i4'), ('tw', '<i4'), ('left', '<i4'),
+                             ('top', '<i4'), ('H', '<i4'), ('W', '<i4')])
+assert IMAGE_DESC_DTYPE.itemsize == ctypes.sizeof(ImageDesc) == 48
+
+PP_PRE_F32, PP_PRE_F16, PP_PRE_BF16, PP_PRE_U8 = 0, 1, 2, 3
+PP_PRE_PLANAR, PP_PRE_CHANNELS_LAST = 0, 1
+
+
 ROLE_CIF, ROLE_CAF, ROLE_HRMAP = 1, 2, 4
 
 

@@ -197,6 +197,12 @@ _SIGNATURES = {
                                  _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
     'pp_decode_ragged_cpu': ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
                               _vp, _vp, _i32], ctypes.c_int),
+    # eval preprocessing (csrc/preprocess.hip) and its host twin
+    'pp_preprocess_tables_size': ([_i32], _sz),
+    'pp_preprocess_images': ([_vp, _i64, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                              _sz, _vp], ctypes.c_int),
+    'pp_preprocess_images_cpu': ([_vp, _i64, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+                                 ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -5,6 +5,9 @@ AnnotationDet objects from network-input to image coordinates exactly as the ref
 (float64 offset / scale steps rounded to float32, float32 rotation), through
 pp_annotations_inverse / pp_dets_inverse.  `inverse_records` applies the same kernels to
 whole device batches of decoder records (one meta per image) without leaving the GPU.
+
+The forward direction, eval_coco.preprocess_factory's chain from images to normalised input
+tensors and metas, is `EvalPreprocess` (preprocess.py).
 """
 import copy
 import ctypes
@@ -16,6 +19,7 @@ from . import _device
 from ._abi import ANN_DTYPE, DET_DTYPE
 from ._lib import PPError, call
 from .annotation import AnnotationDet
+from .preprocess import EvalPreprocess  # noqa: F401
 
 
 class InverseMeta(ctypes.Structure):
