@@ -1284,6 +1284,61 @@ int pp_preprocess_images_cpu(const uint8_t *src, int64_t src_bytes, const pp_ima
                              int32_t layout, const float *mean, const float *std,
                              const uint8_t *fill);
 
+/*
+ * Eval preprocessing with the options of eval_coco.preprocess_factory and the input pyramid
+ * of a multi-scale model, in one launch: the chain of pp_preprocess_images, then
+ *   * a turn of the square padded image by rot * 90 degrees (eval_coco.py:376-384
+ *     --orientation-invariant, transforms/rotate.py:42-52 RotateBy90's swapaxes and flips):
+ *     with N = H = W and `canvas` the padded image,
+ *       rot 1: T[y][x] = canvas[x][N-1-y]; rot 2: canvas[N-1-y][N-1-x]; rot 3: canvas[N-1-x][y];
+ *   * the reduced inputs of network/nets.py:111-131 ShellMultiScale.forward: `reductions` is
+ *     a mask of PP_VIEW_R1 (every pixel), PP_VIEW_R1_5 (rows and columns with i % 3 != 2, at
+ *     i - i / 3), PP_VIEW_R2, PP_VIEW_R3, PP_VIEW_R5 (i % r == 0, at i / r); with `mirror`
+ *     each is followed by its torch.flip(dims=[3]) (column sx at n - 1 - sx, channels not
+ *     swapped).  The views are ordered as nets.py:115-116 orders them: the selected reductions
+ *     ascending, then (mirror) the same mirrored: n_views = popcount(reductions) * (mirror ?
+ *     2 : 1).  PP_VIEW_R1 alone without mirror is the plain turned image.
+ * --extended-scale (eval_coco.py:359-366) needs nothing here: every image carries its own
+ * rescaled size (th, tw) and pad.
+ * images is a HOST table (pp_view_image: pp_image_desc without out_offset, with rot);
+ * view_offsets a HOST (n_img, n_views) table: the first element of image i's region in view
+ * v inside d_out, a region being (3, n_r, n_c) or (n_r, n_c, 3) elements with n = ceil(N / r),
+ * or N - N / 3 for reduction 1.5.  Both are checked on the host and staged into d_tables
+ * (pp_preprocess_views_tables_size(n_img, n_views) bytes, 8-byte aligned) with the value
+ * table.  dtype, layout, mean, std, fill, src_offset and out_elems as pp_preprocess_images.
+ * Each padded pixel is computed once and stored into every view that keeps it.
+ * PP_ESHAPE: everything pp_preprocess_images refuses with it, rot != 0 with H != W, more
+ * than PP_VIEW_R1 alone (or mirror) with H != W, a view region beyond the output buffer.
+ * PP_EINVAL: an empty or unknown reduction mask, rot outside 0..3, an unknown dtype or layout, a
+ * NULL pointer with n_img > 0, a std entry that is 0 or not finite, a misaligned output or
+ * d_tables.  PP_ENOMEM: tables_bytes too small.  n_img == 0 succeeds and launches nothing.
+ */
+enum { PP_VIEW_R1 = 1, PP_VIEW_R1_5 = 2, PP_VIEW_R2 = 4, PP_VIEW_R3 = 8, PP_VIEW_R5 = 16 };
+typedef struct pp_view_image {
+    int64_t src_offset;   /* first byte of the source image in the source buffer     */
+    int32_t h, w;         /* source size                                              */
+    int32_t th, tw;       /* size after the rescale (th == h, tw == w: no rescale)    */
+    int32_t left, top;    /* pad before the rescaled image                            */
+    int32_t H, W;         /* padded size                                              */
+    int32_t rot;          /* 0, 1, 2, 3: turned by 0, 90, 180, 270 degrees            */
+    int32_t reserved;     /* 0                                                        */
+} pp_view_image;
+/* bytes of d_tables for n_img images and n_views views (0 when either is <= 0) */
+size_t pp_preprocess_views_tables_size(int32_t n_img, int32_t n_views);
+/* eval_coco.py:359-384 and nets.py:111-131 on the device, one launch on `stream` */
+int pp_preprocess_views(const uint8_t *d_src, int64_t src_bytes, const pp_view_image *images,
+                        const int64_t *view_offsets, int32_t n_img, int32_t reductions,
+                        int32_t mirror, void *d_out, int64_t out_elems, int32_t dtype,
+                        int32_t layout, const float *mean, const float *std, const uint8_t *fill,
+                        void *d_tables, size_t tables_bytes, void *stream);
+/* the host twin of pp_preprocess_views on host pointers: the same checks and the same
+ * per-pixel code (eval_coco.py:359-384, nets.py:111-131), bit-identical outputs */
+int pp_preprocess_views_cpu(const uint8_t *src, int64_t src_bytes, const pp_view_image *images,
+                            const int64_t *view_offsets, int32_t n_img, int32_t reductions,
+                            int32_t mirror, void *out, int64_t out_elems, int32_t dtype,
+                            int32_t layout, const float *mean, const float *std,
+                            const uint8_t *fill);
+
 #ifdef __cplusplus
 }
 #endif

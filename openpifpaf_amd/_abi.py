@@ -241,6 +241,24 @@ PP_PRE_F32, PP_PRE_F16, PP_PRE_BF16, PP_PRE_U8 = 0, 1, 2, 3
 PP_PRE_PLANAR, PP_PRE_CHANNELS_LAST = 0, 1
 
 
+class ViewImage(ctypes.Structure):
+    """pp_view_image: one image of pp_preprocess_views."""
+    _fields_ = [('src_offset', ctypes.c_int64), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+                ('th', ctypes.c_int32), ('tw', ctypes.c_int32), ('left', ctypes.c_int32),
+                ('top', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('rot', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+VIEW_IMAGE_DTYPE = np.dtype([('src_offset', '<i8'), ('h', '<i4'), ('w', '<i4'), ('th', '<i4'),
+                             ('tw', '<i4'), ('left', '<i4'), ('top', '<i4'), ('H', '<i4'),
+                             ('W', '<i4'), ('rot', '<i4'), ('reserved', '<i4')])
+assert VIEW_IMAGE_DTYPE.itemsize == ctypes.sizeof(ViewImage) == 48
+
+# pp_preprocess_views' reduction mask, in the order of the views (network/nets.py:116)
+PP_VIEW_R1, PP_VIEW_R1_5, PP_VIEW_R2, PP_VIEW_R3, PP_VIEW_R5 = 1, 2, 4, 8, 16
+PP_VIEW_ALL = 31
+
+
 ROLE_CIF, ROLE_CAF, ROLE_HRMAP = 1, 2, 4
 
 

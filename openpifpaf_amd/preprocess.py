@@ -72,12 +72,15 @@ def normalize_annotations(anns):
 class _Plan:
     """Sizes of one image through the chain."""
 
-    def __init__(self, h, w, long_edge, tight):
+    def __init__(self, h, w, long_edge, tight, rescale_edge=None):
+        """rescale_edge: the image's own RescaleAbsolute edge where it is not long_edge
+        (eval_coco.py:359-366 extended_scale); the pad target stays long_edge."""
         if h < 2 or w < 2:
             raise ValueError('image edges must be at least 2 pixels, got {}x{}'.format(h, w))
         self.h, self.w = h, w
-        self.rescale = bool(long_edge)
-        self.th, self.tw = rescaled_size(h, w, long_edge) if long_edge else (h, w)
+        edge = long_edge if rescale_edge is None else rescale_edge
+        self.rescale = bool(edge)
+        self.th, self.tw = rescaled_size(h, w, edge) if edge else (h, w)
         if self.th < 2 or self.tw < 2:
             raise ValueError('rescaled edges must be at least 2 pixels, got {}x{}'
                              .format(self.th, self.tw))
@@ -144,6 +147,40 @@ def _grown(buf, n, make):
     if buf is not None and buf.numel() >= n:
         return buf
     return make(max(n + n // 2, 1024))
+
+
+def _gather_sources(owner, images, descs, src_bytes, dev):
+    """The batch's source images packed into owner._src on the device at their descriptors'
+    src_offset: host images through owner._staging (pinned; owner._staged is the event of the
+    last copy out of it) in one copy, device images gathered on the device.  EvalPreprocess
+    and preprocess_views.EvalViews both stage this way."""
+    owner._src = _grown(owner._src, src_bytes,
+                        lambda m: torch.empty(m, dtype=torch.uint8, device=dev))
+    host = [i for i, im in enumerate(images) if not _device.is_device(im)]
+    if host:
+        owner._staging = _grown(owner._staging, src_bytes,
+                                lambda m: torch.empty(m, dtype=torch.uint8, pin_memory=True))
+        if owner._staged is not None:
+            owner._staged.synchronize()  # the previous batch has left the staging buffer
+        stage = owner._staging.numpy()
+        for i in host:
+            o = int(descs[i]['src_offset'])
+            im = images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]
+            stage[o:o + im.size] = im.reshape(-1)
+        # one copy from the first to the last host image (device images in between are
+        # written after it)
+        lo, last = int(descs[host[0]]['src_offset']), descs[host[-1]]
+        hi = int(last['src_offset']) + int(last['h']) * int(last['w']) * 3
+        owner._src[lo:hi].copy_(owner._staging[lo:hi], non_blocking=True)
+        owner._staged = torch.cuda.Event()
+        owner._staged.record()
+    if not host:  # every image on the device: one gather launch
+        torch.cat([im.reshape(-1) for im in images], out=owner._src[:src_bytes])
+    else:
+        for i, im in enumerate(images):
+            if _device.is_device(im):
+                o = int(descs[i]['src_offset'])
+                owner._src[o:o + im.numel()].view(im.shape).copy_(im)
 
 
 class EvalPreprocess:
@@ -266,33 +303,7 @@ class EvalPreprocess:
         flat = out[:out_elems]
         if n == 0:
             return self._results(flat, plans, descs), out_metas
-        self._src = _grown(self._src, src_bytes,
-                           lambda m: torch.empty(m, dtype=torch.uint8, device=dev))
-        host = [i for i, im in enumerate(images) if not _device.is_device(im)]
-        if host:
-            self._staging = _grown(self._staging, src_bytes,
-                                   lambda m: torch.empty(m, dtype=torch.uint8, pin_memory=True))
-            if self._staged is not None:
-                self._staged.synchronize()  # the previous batch has left the staging buffer
-            stage = self._staging.numpy()
-            for i in host:
-                o = int(descs[i]['src_offset'])
-                im = images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]
-                stage[o:o + im.size] = im.reshape(-1)
-            # one copy from the first to the last host image (device images in between are
-            # written after it)
-            lo, last = int(descs[host[0]]['src_offset']), descs[host[-1]]
-            hi = int(last['src_offset']) + int(last['h']) * int(last['w']) * 3
-            self._src[lo:hi].copy_(self._staging[lo:hi], non_blocking=True)
-            self._staged = torch.cuda.Event()
-            self._staged.record()
-        if not host:  # every image on the device: one gather launch
-            torch.cat([im.reshape(-1) for im in images], out=self._src[:src_bytes])
-        else:
-            for i, im in enumerate(images):
-                if _device.is_device(im):
-                    o = int(descs[i]['src_offset'])
-                    self._src[o:o + im.numel()].view(im.shape).copy_(im)
+        _gather_sources(self, images, descs, src_bytes, dev)
         self._launch(descs, src_bytes, out, out_elems)
         return self._results(flat, plans, descs), out_metas
 

@@ -7,7 +7,8 @@ pp_annotations_inverse / pp_dets_inverse.  `inverse_records` applies the same ke
 whole device batches of decoder records (one meta per image) without leaving the GPU.
 
 The forward direction, eval_coco.preprocess_factory's chain from images to normalised input
-tensors and metas, is `EvalPreprocess` (preprocess.py).
+tensors and metas, is `EvalPreprocess` (preprocess.py), and with the reference's extended
+scale, turns and multi-scale input pyramid `EvalViews` (preprocess_views.py).
 """
 import copy
 import ctypes
@@ -20,6 +21,7 @@ from ._abi import ANN_DTYPE, DET_DTYPE
 from ._lib import PPError, call
 from .annotation import AnnotationDet
 from .preprocess import EvalPreprocess  # noqa: F401
+from .preprocess_views import EvalViews  # noqa: F401
 
 
 class InverseMeta(ctypes.Structure):
