@@ -1339,6 +1339,109 @@ int pp_preprocess_views_cpu(const uint8_t *src, int64_t src_bytes, const pp_view
                             int32_t layout, const float *mean, const float *std,
                             const uint8_t *fill);
 
+/*
+ * CIF and CAF target encoders (openpifpaf/encoder/cif.py, caf.py, annrescaler.py and
+ * utils.py:6-37 create_sink, mask_valid_area) for a batch of images in one launch per
+ * encoder.  The tensors are bit for bit the reference's (NumPy 2 promotion rules, NaN as
+ * 0x7FC00000).
+ *
+ * All inputs are HOST tables.  The call checks them, restates the per-annotation scalars
+ * of the reference on the host (annrescaler.py:39-47 keypoint_sets /= stride, 49-75 bg_mask
+ * boxes, 77-109 scale; cif.py:87-101 max_r by quadrant, 113-114 joint_scale, 119-126 the
+ * patch's place and offset; caf.py:100-114 shortest_sparse, 124-144 the dense-to-sparse and
+ * field-of-view tests, 164-177 offset, num, fmargin and the linspace), stages the resulting
+ * job lists into d_tables on `stream` (pp_encode_*_tables_size bytes are always enough;
+ * 8-byte aligned) and launches one kernel, asynchronously.  The rasterisation
+ * (cif.py:129-145, caf.py:180-222) and fields() (cif.py:147-162, caf.py:224-246: the crop
+ * of the padding, the bg_mask NaN, mask_valid_area) are the kernel: every output element is
+ * stored exactly once, nothing is cleared first.
+ *
+ *   images     n_img records: pixel size, the field size (h, w) = ((height - 1) / stride + 1,
+ *              (width - 1) / stride + 1), meta['valid_area'] in pixels (x, y, w, h) when
+ *              has_valid_area, the image's annotations anns[ann0 .. ann0 + n_ann) and the
+ *              first element of each of its output tensors in d_out:
+ *                CIF  (K, h, w), (K, 6, h, w), (K, h, w)                       out_offset[0..2]
+ *                CAF  (C, h, w), (C, 6, h, w), (C, 6, h, w), (C, h, w), (C, h, w)   [0..4]
+ *              all float32.  Images of one size whose regions are adjacent per tensor stack
+ *              to (B, ...).
+ *   anns       per annotation: bbox (x, y, w, h) float32 in pixels, iscrowd, and flags
+ *              PP_ENC_HAS_KEYPOINTS / PP_ENC_HAS_BBOX ('keypoints' in ann, 'bbox' in ann)
+ *   keypoints  (n_ann, K, 3) float32 (x, y, v) in pixels; rows of annotations without
+ *              keypoints are not read
+ *   enc        the encoder: pose and pose_45 (K, 2) doubles (annrescaler.py:18-26; the
+ *              total areas are derived here), sigmas (K doubles, used as Python floats, or
+ *              NULL), v_threshold, side (Cif.side_length / Caf.min_size, 1..8), padding
+ *              (0..64), stride; for CAF the 1-based skeleton (C, 2), the sparse skeleton
+ *              (n_sparse, 2) or NULL, dense_to_sparse_radius, only_in_field_of_view,
+ *              fixed_size and aspect_ratio.
+ *
+ * Refused before any launch.  PP_EINVAL: a NULL argument, a misaligned or NULL table block,
+ * aspect_ratio != 0 ("aspect_ratio": the patch side would grow with the limb; not built), a
+ * non-finite coordinate of a joint with v > v_threshold, an annotation that the reference
+ * would need a key from that it lacks, a joint scale <= 0 that reaches the reference's
+ * `assert scale > 0.0` (cif.py:144, caf.py:219-221).  PP_ESHAPE: K outside [1, PP_MAX_KP],
+ * C outside [1, PP_MAX_EDGES], a skeleton index outside 1..K, side outside 1..8, padding
+ * outside 0..64, stride < 1, a field size that is not the pixel size's or beyond 16384, an
+ * annotation range outside [0, n_ann), an output region outside d_out.  PP_ENOMEM:
+ * tables_bytes too small.  n_img == 0 succeeds and launches nothing.
+ *
+ * pp_encode_cif_cpu / pp_encode_caf_cpu are the host twins on host pointers: the same plan
+ * and the same per-cell code, one image per task on n_threads host threads (< 1: one).
+ */
+enum { PP_ENC_HAS_KEYPOINTS = 1, PP_ENC_HAS_BBOX = 2 };
+typedef struct pp_enc_image {
+    int64_t out_offset[5];  /* first element of each output tensor of this image         */
+    double valid_area[4];   /* meta['valid_area'] (x, y, w, h) in pixels                 */
+    int32_t has_valid_area; /* 'valid_area' in meta                                      */
+    int32_t height, width;  /* pixels                                                    */
+    int32_t h, w;           /* field size                                                */
+    int32_t ann0, n_ann;    /* this image's annotations                                  */
+    int32_t reserved;       /* 0                                                         */
+} pp_enc_image;
+typedef struct pp_enc_ann {
+    float bbox[4];
+    int32_t iscrowd;
+    int32_t flags;          /* PP_ENC_HAS_*                                              */
+} pp_enc_ann;
+typedef struct pp_encoder {
+    const double *pose;             /* (K, 2) */
+    const double *pose_45;          /* (K, 2) */
+    const double *sigmas;           /* (K) or NULL */
+    const int32_t *skeleton;        /* CAF: (C, 2), 1-based */
+    const int32_t *sparse_skeleton; /* CAF: (n_sparse, 2), 1-based, or NULL */
+    double v_threshold;
+    double dense_to_sparse_radius;
+    double aspect_ratio;            /* must be 0 */
+    int32_t stride, K, C, n_sparse;
+    int32_t side;                   /* Cif.side_length / Caf.min_size */
+    int32_t padding;
+    int32_t only_in_field_of_view, fixed_size;
+} pp_encoder;
+/* bytes of d_tables that are enough for any batch of n_img images and n_ann annotations */
+size_t pp_encode_cif_tables_size(int32_t n_img, int32_t n_ann, int32_t K);
+size_t pp_encode_caf_tables_size(int32_t n_img, int32_t n_ann, int32_t C);
+/* float32 elements of one image's tensors together: 8 K h w and 15 C h w (0: bad shape) */
+int64_t pp_encode_cif_output_size(int32_t h, int32_t w, int32_t K);
+int64_t pp_encode_caf_output_size(int32_t h, int32_t w, int32_t C);
+/* encoder/cif.py:25-162 CifGenerator for a batch, one launch on `stream` */
+int pp_encode_cif(const pp_encoder *enc, const pp_enc_image *images, int32_t n_img,
+                  const pp_enc_ann *anns, const float *keypoints, int32_t n_ann, float *d_out,
+                  int64_t out_elems, void *d_tables, size_t tables_bytes, void *stream);
+/* encoder/caf.py:32-246 CafGenerator for a batch, one launch on `stream` */
+int pp_encode_caf(const pp_encoder *enc, const pp_enc_image *images, int32_t n_img,
+                  const pp_enc_ann *anns, const float *keypoints, int32_t n_ann, float *d_out,
+                  int64_t out_elems, void *d_tables, size_t tables_bytes, void *stream);
+int pp_encode_cif_cpu(const pp_encoder *enc, const pp_enc_image *images, int32_t n_img,
+                      const pp_enc_ann *anns, const float *keypoints, int32_t n_ann, float *out,
+                      int64_t out_elems, int32_t n_threads);
+int pp_encode_caf_cpu(const pp_encoder *enc, const pp_enc_image *images, int32_t n_img,
+                      const pp_enc_ann *anns, const float *keypoints, int32_t n_ann, float *out,
+                      int64_t out_elems, int32_t n_threads);
+/* the twins' helpers, for tests against NumPy: np.linalg.norm of n float32 pairs (caf.py:111,
+ * 165; cif.py:99) and np.linspace(start, stop, num) for num >= 2 (caf.py:177) */
+int pp_encode_norm_cpu(const float *xy, float *out, int64_t n);
+int pp_encode_linspace_cpu(double start, double stop, int32_t num, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -259,6 +259,28 @@ PP_VIEW_R1, PP_VIEW_R1_5, PP_VIEW_R2, PP_VIEW_R3, PP_VIEW_R5 = 1, 2, 4, 8, 16
 PP_VIEW_ALL = 31
 
 
+class Encoder(ctypes.Structure):
+    """pp_encoder: one CIF or CAF target encoder (pp_encode_cif / pp_encode_caf)."""
+    _fields_ = [('pose', ctypes.c_void_p), ('pose_45', ctypes.c_void_p),
+                ('sigmas', ctypes.c_void_p), ('skeleton', ctypes.c_void_p),
+                ('sparse_skeleton', ctypes.c_void_p), ('v_threshold', ctypes.c_double),
+                ('dense_to_sparse_radius', ctypes.c_double), ('aspect_ratio', ctypes.c_double),
+                ('stride', ctypes.c_int32), ('K', ctypes.c_int32), ('C', ctypes.c_int32),
+                ('n_sparse', ctypes.c_int32), ('side', ctypes.c_int32),
+                ('padding', ctypes.c_int32), ('only_in_field_of_view', ctypes.c_int32),
+                ('fixed_size', ctypes.c_int32)]
+
+
+# pp_enc_image and pp_enc_ann: the host tables of pp_encode_cif / pp_encode_caf
+ENC_IMAGE_DTYPE = np.dtype([('out_offset', '<i8', (5,)), ('valid_area', '<f8', (4,)),
+                            ('has_valid_area', '<i4'), ('height', '<i4'), ('width', '<i4'),
+                            ('h', '<i4'), ('w', '<i4'), ('ann0', '<i4'), ('n_ann', '<i4'),
+                            ('reserved', '<i4')])
+ENC_ANN_DTYPE = np.dtype([('bbox', '<f4', (4,)), ('iscrowd', '<i4'), ('flags', '<i4')])
+assert ENC_IMAGE_DTYPE.itemsize == 104 and ENC_ANN_DTYPE.itemsize == 24
+PP_ENC_HAS_KEYPOINTS, PP_ENC_HAS_BBOX = 1, 2
+
+
 ROLE_CIF, ROLE_CAF, ROLE_HRMAP = 1, 2, 4
 
 

@@ -209,6 +209,17 @@ _SIGNATURES = {
                              _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
     'pp_preprocess_views_cpu': ([_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _i32,
                                  _vp, _vp, _vp], ctypes.c_int),
+    # CIF / CAF target encoders (csrc/encode.hip) and their host twins (csrc/encode_cpu.hip)
+    'pp_encode_cif_tables_size': ([_i32, _i32, _i32], _sz),
+    'pp_encode_caf_tables_size': ([_i32, _i32, _i32], _sz),
+    'pp_encode_cif_output_size': ([_i32, _i32, _i32], _i64),
+    'pp_encode_caf_output_size': ([_i32, _i32, _i32], _i64),
+    'pp_encode_cif': ([_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _sz, _vp], ctypes.c_int),
+    'pp_encode_caf': ([_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _sz, _vp], ctypes.c_int),
+    'pp_encode_cif_cpu': ([_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32], ctypes.c_int),
+    'pp_encode_caf_cpu': ([_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32], ctypes.c_int),
+    'pp_encode_norm_cpu': ([_vp, _vp, _i64], ctypes.c_int),
+    'pp_encode_linspace_cpu': ([_f64, _f64, _i32, _vp], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -255,3 +255,30 @@ def digest(*arrays):
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
+
+
+def fields_from_targets(cif_targets, caf_targets):
+    """Decoder input from encoder targets (encoder.Cif / encoder.Caf batches, or NumPy
+    tensors of the same shapes): (cif (B, K, 5, h, w), caf (B, C, 9, h, w)) on the device,
+    arranged as CifCafCollector does (network/heads.py:78-88) with b = 1.  NaN confidences
+    become 0, the regressions get the index grid added, NaN scales and regressions become 0.
+    torch ops only."""
+    import torch  # pylint: disable=import-outside-toplevel
+    from . import _device  # pylint: disable=import-outside-toplevel
+
+    def clean(t):
+        return torch.where(torch.isnan(t), torch.zeros_like(t), t)
+
+    conf, reg, scale = (_device.to_device(t) for t in cif_targets)
+    h, w = conf.shape[-2:]
+    gx = torch.arange(w, dtype=torch.float32, device=conf.device).expand(h, w)
+    gy = torch.arange(h, dtype=torch.float32, device=conf.device).unsqueeze(1).expand(h, w)
+    one = torch.ones_like(conf)
+    cif = torch.stack([clean(conf), clean(reg[:, :, 0] + gx), clean(reg[:, :, 1] + gy), one,
+                       clean(scale)], dim=2)
+    conf, reg1, reg2, scale1, scale2 = (_device.to_device(t) for t in caf_targets)
+    one = torch.ones_like(conf)
+    caf = torch.stack([clean(conf), clean(reg1[:, :, 0] + gx), clean(reg1[:, :, 1] + gy), one,
+                       clean(scale1), clean(reg2[:, :, 0] + gx), clean(reg2[:, :, 1] + gy), one,
+                       clean(scale2)], dim=2)
+    return cif.contiguous(), caf.contiguous()
