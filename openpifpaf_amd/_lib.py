@@ -203,7 +203,7 @@ _SIGNATURES = {
                               _sz, _vp], ctypes.c_int),
     'pp_preprocess_images_cpu': ([_vp, _i64, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
                                  ctypes.c_int),
-    # ... with turns and the input pyramid (csrc/preprocess_views.hip) and its host twin
+    # ... with turns and the input pyramid (csrc/preprocess.hip too) and its host twin
     'pp_preprocess_views_tables_size': ([_i32, _i32], _sz),
     'pp_preprocess_views': ([_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp,
                              _vp, _vp, _vp, _sz, _vp], ctypes.c_int),

@@ -1,6 +1,5 @@
 // preprocess_pixel.hpp — the per-pixel code of the eval preprocessing kernels
-// (preprocess.hip: pp_preprocess_images; preprocess_views.hip: pp_preprocess_views) and of
-// their host twins: the image record, the zoom of one axis, the bilinear blend, the taps of
+// (preprocess.hip: pp_preprocess_images and pp_preprocess_views) and of their host twin: the image record, the zoom of one axis, the bilinear blend, the taps of
 // one output pixel, the padded pixel, the output index and store, and the host's value table.
 // Every function a kernel calls is __host__ __device__, so a kernel and its twin agree bit
 // for bit by construction.  preprocess.hip's head comment has the arithmetic and why no

@@ -8,6 +8,9 @@ RescaleAbsolute(long_edge), CenterPad(long_edge) or CenterPadTight(16) and EVAL_
 consume); `EvalPreprocess.__call__` has the reference's per-image signature; `batch_cpu` runs
 the host twin and is only ever used when called by name.  The metas and the annotations are
 host NumPy work in float64 / float32 with exactly the chain's operations.
+
+The planner, the source staging, the buffers and the entry points are `_EvalChain`'s, which
+preprocess_views.EvalViews (the chain's options and the input pyramid) shares.
 """
 import copy
 import ctypes
@@ -18,7 +21,7 @@ import torch
 
 from . import _device
 from ._abi import (IMAGE_DESC_DTYPE, PP_PRE_BF16, PP_PRE_CHANNELS_LAST, PP_PRE_F16, PP_PRE_F32,
-                   PP_PRE_PLANAR, PP_PRE_U8)
+                   PP_PRE_PLANAR, PP_PRE_U8, VIEW_IMAGE_DTYPE)
 from ._lib import call, load
 
 # transforms/__init__.py:24-25 and pad.py:51
@@ -71,6 +74,8 @@ def normalize_annotations(anns):
 
 class _Plan:
     """Sizes of one image through the chain."""
+
+    rot = 0  # quarter turns (preprocess_views._ViewPlan)
 
     def __init__(self, h, w, long_edge, tight, rescale_edge=None):
         """rescale_edge: the image's own RescaleAbsolute edge where it is not long_edge
@@ -149,54 +154,63 @@ def _grown(buf, n, make):
     return make(max(n + n // 2, 1024))
 
 
-def _gather_sources(owner, images, descs, src_bytes, dev):
-    """The batch's source images packed into owner._src on the device at their descriptors'
-    src_offset: host images through owner._staging (pinned; owner._staged is the event of the
-    last copy out of it) in one copy, device images gathered on the device.  EvalPreprocess
-    and preprocess_views.EvalViews both stage this way."""
-    owner._src = _grown(owner._src, src_bytes,
-                        lambda m: torch.empty(m, dtype=torch.uint8, device=dev))
-    host = [i for i, im in enumerate(images) if not _device.is_device(im)]
-    if host:
-        owner._staging = _grown(owner._staging, src_bytes,
-                                lambda m: torch.empty(m, dtype=torch.uint8, pin_memory=True))
-        if owner._staged is not None:
-            owner._staged.synchronize()  # the previous batch has left the staging buffer
-        stage = owner._staging.numpy()
-        for i in host:
-            o = int(descs[i]['src_offset'])
-            im = images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]
-            stage[o:o + im.size] = im.reshape(-1)
-        # one copy from the first to the last host image (device images in between are
-        # written after it)
-        lo, last = int(descs[host[0]]['src_offset']), descs[host[-1]]
-        hi = int(last['src_offset']) + int(last['h']) * int(last['w']) * 3
-        owner._src[lo:hi].copy_(owner._staging[lo:hi], non_blocking=True)
-        owner._staged = torch.cuda.Event()
-        owner._staged.record()
-    if not host:  # every image on the device: one gather launch
-        torch.cat([im.reshape(-1) for im in images], out=owner._src[:src_bytes])
-    else:
-        for i, im in enumerate(images):
-            if _device.is_device(im):
+def _vp(array):
+    return array.ctypes.data_as(ctypes.c_void_p)
+
+
+class _Sources:
+    """The source images of a batch packed into one device buffer (`src`) at their rows'
+    src_offset: host images through a pinned staging buffer in one copy, device images
+    gathered on the device."""
+
+    def __init__(self):
+        self.src = self._staging = None
+        self._staged = None  # event: the last copy out of the staging buffer
+
+    def gather(self, images, descs, src_bytes, dev):
+        self.src = _grown(self.src, src_bytes,
+                          lambda m: torch.empty(m, dtype=torch.uint8, device=dev))
+        host = [i for i, im in enumerate(images) if not _device.is_device(im)]
+        if host:
+            self._staging = _grown(self._staging, src_bytes,
+                                   lambda m: torch.empty(m, dtype=torch.uint8, pin_memory=True))
+            if self._staged is not None:
+                self._staged.synchronize()  # the previous batch has left the staging buffer
+            stage = self._staging.numpy()
+            for i in host:
                 o = int(descs[i]['src_offset'])
-                owner._src[o:o + im.numel()].view(im.shape).copy_(im)
+                im = images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]
+                stage[o:o + im.size] = im.reshape(-1)
+            # one copy from the first to the last host image (device images in between are
+            # written after it)
+            lo, last = int(descs[host[0]]['src_offset']), descs[host[-1]]
+            hi = int(last['src_offset']) + int(last['h']) * int(last['w']) * 3
+            self.src[lo:hi].copy_(self._staging[lo:hi], non_blocking=True)
+            self._staged = torch.cuda.Event()
+            self._staged.record()
+        if not host:  # every image on the device: one gather launch
+            torch.cat([im.reshape(-1) for im in images], out=self.src[:src_bytes])
+        else:
+            for i, im in enumerate(images):
+                if _device.is_device(im):
+                    o = int(descs[i]['src_offset'])
+                    self.src[o:o + im.numel()].view(im.shape).copy_(im)
 
 
-class EvalPreprocess:
-    """eval_coco.preprocess_factory(long_edge, tight_padding=...) for uint8 RGB images.
+class _EvalChain:
+    """What EvalPreprocess and preprocess_views.EvalViews share: the refusals of both, the
+    planner, the output and table buffers and the entry points.  A subclass gives the plan of
+    one image (`_view_plan(h, w, meta)`: a _Plan), the device call (`_launch`) and the twin
+    call (`_twin`); with `_view_edges` set (the edges of the pyramid's views) a batch is a
+    list of views, without it one canvas per image."""
 
-    dtype: torch.float32, float16 or bfloat16 (the float32 tensor's `.to(dtype)`), or
-    torch.uint8 for the padded (H, W, 3) image the reference holds before ToTensor.
-    channels_last: the (3, H, W) tensors are views of (H, W, 3) memory."""
+    _view_edges = None
 
-    def __init__(self, long_edge, *, tight_padding=False, dtype=torch.float32,
-                 channels_last=False, extended_scale=False, orientation_invariant=False,
-                 fast=False, resample=_BILINEAR):
-        if extended_scale:
-            raise NotImplementedError('extended_scale')
-        if orientation_invariant:
-            raise NotImplementedError('orientation_invariant')
+    @property
+    def n_views(self):
+        return len(self._view_edges) if self._view_edges else 1
+
+    def __init__(self, long_edge, tight_padding, dtype, channels_last, fast, resample):
         if fast:
             raise NotImplementedError('fast=True (PIL resize)')
         if resample not in (_BILINEAR, 'bilinear'):
@@ -216,8 +230,8 @@ class EvalPreprocess:
         self._mean = np.asarray(MEAN, np.float32)
         self._std = np.asarray(STD, np.float32)
         self._fill = np.asarray(FILL, np.uint8)
-        self._staging = self._src = self._tables = self._out = None
-        self._staged = None  # event: the last copy out of the staging buffer
+        self._sources = _Sources()
+        self._tables = self._out = None
 
     # ---------------------------------------------------------------- host-side planning
     @staticmethod
@@ -231,28 +245,39 @@ class EvalPreprocess:
         return image, (int(image.shape[0]), int(image.shape[1]))
 
     def _plan(self, images, metas):
+        """(images, plans, rows, offsets, src_bytes, out_elems, metas): the VIEW_IMAGE_DTYPE
+        rows and the (n, n_views) first elements of every image in every view.  The output
+        holds view after view, each with its images in order."""
         if metas is None:
             metas = [None] * len(images)
         if len(metas) != len(images):
             raise ValueError('{} metas for {} images'.format(len(metas), len(images)))
         images = [self._shape(im) for im in images]
-        plans = [_Plan(h, w, self.long_edge, self.tight_padding) for _, (h, w) in images]
-        descs = np.zeros(len(plans), IMAGE_DESC_DTYPE)
-        src_off = out_off = 0
-        for d, p in zip(descs, plans):
-            d['src_offset'], d['out_offset'] = src_off, out_off
-            d['h'], d['w'], d['th'], d['tw'] = p.h, p.w, p.th, p.tw
-            d['left'], d['top'], d['H'], d['W'] = p.ltrb[0], p.ltrb[1], p.H, p.W
-            src_off += p.h * p.w * 3
-            out_off += p.H * p.W * 3
+        plans = [self._view_plan(h, w, m) for (_, (h, w)), m in zip(images, metas)]
+        n = len(plans)
+        names = ('h', 'w', 'th', 'tw', 'left', 'top', 'H', 'W', 'rot')
+        cols = np.array([(p.h, p.w, p.th, p.tw, p.ltrb[0], p.ltrb[1], p.H, p.W, p.rot)
+                         for p in plans], np.int64).reshape(n, len(names)).T
+        rows = np.zeros(n, VIEW_IMAGE_DTYPE)
+        for name, col in zip(names, cols):
+            rows[name] = col
+        src_sizes = 3 * cols[0] * cols[1]
+        rows['src_offset'] = np.cumsum(src_sizes) - src_sizes
+        if self._view_edges:
+            sizes = np.repeat(3 * np.square(np.array(self._view_edges, np.int64)), n)
+        else:
+            sizes = 3 * cols[6] * cols[7]
+        offsets = np.ascontiguousarray((np.cumsum(sizes) - sizes).reshape(self.n_views, n).T)
         out_metas = [p.meta(m) for p, m in zip(plans, metas)]
-        return [im for im, _ in images], plans, descs, src_off, out_off, out_metas
+        return ([im for im, _ in images], plans, rows, offsets, int(src_sizes.sum()),
+                int(sizes.sum()), out_metas)
 
-    def _results(self, flat, plans, descs):
+    def _results(self, flat, plans, offsets):
         """The results as views of the flat output (a torch tensor or a NumPy array of
         exactly the batch's elements): CenterPad, one (B, 3, L, L) array (every image is
-        L x L and the regions are adjacent); tight padding, a (1, 3, H_i, W_i) view per image.
-        uint8: (B, L, L, 3), or (H_i, W_i, 3) per image."""
+        L x L and the regions are adjacent); tight padding, a (1, 3, H_i, W_i) view per image;
+        a pyramid, a list of (B, 3, n_v, n_v) arrays.  uint8: (B, L, L, 3), (H_i, W_i, 3) per
+        image, (B, n_v, n_v, 3)."""
         def shaped(o, lead, h, w):
             if self.dtype == torch.uint8:
                 return o.reshape(lead + (h, w, 3))
@@ -263,76 +288,119 @@ class EvalPreprocess:
             axes = tuple(range(k)) + (k + 2, k, k + 1)
             return o.permute(*axes) if isinstance(o, torch.Tensor) else o.transpose(*axes)
 
+        n = len(plans)
+        if self._view_edges:
+            ends = np.cumsum([3 * s * s * n for s in self._view_edges]).tolist()
+            return [shaped(flat[e - 3 * s * s * n:e], (n,), s, s)
+                    for s, e in zip(self._view_edges, ends)]
         if not self.tight_padding:
-            return shaped(flat, (len(plans),), self.long_edge, self.long_edge)
+            return shaped(flat, (n,), self.long_edge, self.long_edge)
         lead = () if self.dtype == torch.uint8 else (1,)
-        return [shaped(flat[int(d['out_offset']):int(d['out_offset']) + 3 * p.H * p.W], lead,
-                       p.H, p.W) for d, p in zip(descs, plans)]
+        return [shaped(flat[o:o + 3 * p.H * p.W], lead, p.H, p.W)
+                for o, p in zip(offsets[:, 0].tolist(), plans)]
 
-    def _layout(self):
-        return PP_PRE_CHANNELS_LAST if self.channels_last else PP_PRE_PLANAR
+    def _format(self):
+        """dtype, layout, mean, std, fill as every entry takes them."""
+        return (_DTYPES[self.dtype][0],
+                PP_PRE_CHANNELS_LAST if self.channels_last else PP_PRE_PLANAR,
+                _vp(self._mean), _vp(self._std), _vp(self._fill))
 
-    def _launch(self, descs, src_bytes, out, out_elems):
-        """pp_preprocess_images over the gathered source buffer on _device.stream()."""
-        n = len(descs)
-        tables_bytes = load().pp_preprocess_tables_size(n)
-        self._tables = _grown(self._tables, tables_bytes,
-                              lambda m: torch.empty(m, dtype=torch.uint8, device=out.device))
-        call('pp_preprocess_images', _device.ptr(self._src), src_bytes,
-             descs.ctypes.data_as(ctypes.c_void_p), n, _device.ptr(out), out_elems,
-             _DTYPES[self.dtype][0], self._layout(),
-             self._mean.ctypes.data_as(ctypes.c_void_p),
-             self._std.ctypes.data_as(ctypes.c_void_p),
-             self._fill.ctypes.data_as(ctypes.c_void_p), _device.ptr(self._tables), tables_bytes,
-             _device.stream())
+    def _table_buffer(self, nbytes, dev):
+        """(d_tables, tables_bytes) of a device entry."""
+        self._tables = _grown(self._tables, nbytes,
+                              lambda m: torch.empty(m, dtype=torch.uint8, device=dev))
+        return _device.ptr(self._tables), nbytes
 
     # ---------------------------------------------------------------------- entry points
     def batch(self, images, metas=None, fresh=False):
         """(tensors, metas) of a list of (h, w, 3) uint8 images: anything np.asarray accepts
         (PIL images among them) or torch uint8 tensors on the host or the device.  CenterPad
-        gives one (B, 3, L, L) tensor, tight padding a list of (1, 3, H_i, W_i) views of one
-        allocation.  The tensors are overwritten by the next call unless fresh=True."""
+        gives one (B, 3, L, L) tensor, tight padding a list of (1, 3, H_i, W_i) tensors, a
+        pyramid a list of 5 or 10 tensors (B, 3, n_v, n_v); all are views of one allocation,
+        which the next call overwrites unless fresh=True."""
         dev = _device.require()
-        images, plans, descs, src_bytes, out_elems, out_metas = self._plan(images, metas)
-        n = len(plans)
+        images, plans, rows, offsets, src_bytes, out_elems, out_metas = self._plan(images, metas)
         if fresh:
             out = torch.empty(out_elems, dtype=self.dtype, device=dev)
         else:
             out = self._out = _grown(
                 self._out, out_elems, lambda m: torch.empty(m, dtype=self.dtype, device=dev))
-        flat = out[:out_elems]
-        if n == 0:
-            return self._results(flat, plans, descs), out_metas
-        _gather_sources(self, images, descs, src_bytes, dev)
-        self._launch(descs, src_bytes, out, out_elems)
-        return self._results(flat, plans, descs), out_metas
+        if plans:
+            self._sources.gather(images, rows, src_bytes, dev)
+            self._launch(rows, offsets, src_bytes, out, out_elems)
+        return self._results(out[:out_elems], plans, offsets), out_metas
 
     def batch_cpu(self, images, metas=None):
-        """`batch` through the host twin (pp_preprocess_images_cpu): NumPy arrays of the same
-        shapes; bfloat16 results are their bit patterns as uint16.  Device tensors are not
-        accepted.  Nothing falls back to this."""
-        images, plans, descs, src_bytes, out_elems, out_metas = self._plan(images, metas)
-        n = len(plans)
-        code, np_dtype = _DTYPES[self.dtype]
+        """`batch` through the host twin: NumPy arrays of the same shapes; bfloat16 results
+        are their bit patterns as uint16.  Device tensors are not accepted.  Nothing falls
+        back to this."""
+        images, plans, rows, offsets, src_bytes, out_elems, out_metas = self._plan(images, metas)
         src = np.empty(max(src_bytes, 1), np.uint8)
-        for d, im in zip(descs, images):
+        for o, im in zip(rows['src_offset'].tolist(), images):
             if isinstance(im, torch.Tensor):
                 im = im.numpy()
-            src[int(d['src_offset']):int(d['src_offset']) + im.size] = im.reshape(-1)
-        out = np.empty(out_elems, np_dtype)
-        call('pp_preprocess_images_cpu', src.ctypes.data_as(ctypes.c_void_p), src_bytes,
-             descs.ctypes.data_as(ctypes.c_void_p), n, out.ctypes.data_as(ctypes.c_void_p),
-             out_elems, code, self._layout(), self._mean.ctypes.data_as(ctypes.c_void_p),
-             self._std.ctypes.data_as(ctypes.c_void_p),
-             self._fill.ctypes.data_as(ctypes.c_void_p))
-        return self._results(out, plans, descs), out_metas
+            src[o:o + im.size] = im.reshape(-1)
+        out = np.empty(out_elems, _DTYPES[self.dtype][1])
+        self._twin(_vp(src), src_bytes, rows, offsets, _vp(out), out_elems)
+        return self._results(out, plans, offsets), out_metas
 
     def __call__(self, image, anns, meta):
-        """The reference signature for one image: (tensor (3, H, W), anns, meta)."""
+        """The reference signature for one image: (tensor (3, H, W), anns, meta); with a
+        pyramid the first entry is the list of the image's (3, n_v, n_v) views."""
         _, (h, w) = self._shape(image)
-        plan = _Plan(h, w, self.long_edge, self.tight_padding)
-        tensors, metas = self.batch([image], [meta], fresh=True)
-        tensor = tensors[0]  # CenterPad: the batch's only image
-        if self.tight_padding and self.dtype != torch.uint8:
-            tensor = tensor[0]
-        return tensor, plan.anns(anns), metas[0]
+        plan = self._view_plan(h, w, meta)
+        views, metas = self.batch([image], [meta], fresh=True)
+        if self._view_edges:
+            first = [v[0] for v in views]
+        else:
+            first = views[0]  # CenterPad: the batch's only image
+            if self.tight_padding and self.dtype != torch.uint8:
+                first = first[0]
+        return first, plan.anns(anns), metas[0]
+
+
+def image_descs(rows, offsets):
+    """IMAGE_DESC_DTYPE rows of single-view VIEW_IMAGE_DTYPE rows and their offsets."""
+    descs = np.zeros(len(rows), IMAGE_DESC_DTYPE)
+    for name in ('src_offset', 'h', 'w', 'th', 'tw', 'left', 'top', 'H', 'W'):
+        descs[name] = rows[name]
+    descs['out_offset'] = offsets[:, 0]
+    return descs
+
+
+class EvalPreprocess(_EvalChain):
+    """eval_coco.preprocess_factory(long_edge, tight_padding=...) for uint8 RGB images.
+
+    dtype: torch.float32, float16 or bfloat16 (the float32 tensor's `.to(dtype)`), or
+    torch.uint8 for the padded (H, W, 3) image the reference holds before ToTensor.
+    channels_last: the (3, H, W) tensors are views of (H, W, 3) memory."""
+
+    def __init__(self, long_edge, *, tight_padding=False, dtype=torch.float32,
+                 channels_last=False, extended_scale=False, orientation_invariant=False,
+                 fast=False, resample=_BILINEAR):
+        if extended_scale:
+            raise NotImplementedError('extended_scale')
+        if orientation_invariant:
+            raise NotImplementedError('orientation_invariant')
+        super().__init__(long_edge, tight_padding, dtype, channels_last, fast, resample)
+
+    def _view_plan(self, h, w, meta):  # pylint: disable=unused-argument
+        return _Plan(h, w, self.long_edge, self.tight_padding)
+
+    def _launch(self, rows, offsets, src_bytes, out, out_elems):
+        self._launch_descs(image_descs(rows, offsets), src_bytes, out, out_elems)
+
+    def _launch_descs(self, descs, src_bytes, out, out_elems):
+        """pp_preprocess_images over the gathered source buffer on _device.stream()."""
+        n = len(descs)
+        call('pp_preprocess_images', _device.ptr(self._sources.src), src_bytes, _vp(descs), n,
+             _device.ptr(out), out_elems, *self._format(),
+             *self._table_buffer(load().pp_preprocess_tables_size(n), out.device),
+             _device.stream())
+
+    def _twin(self, src, src_bytes, rows, offsets, out, out_elems):
+        descs = image_descs(rows, offsets)
+        call('pp_preprocess_images_cpu', src, src_bytes, _vp(descs), len(descs), out, out_elems,
+             *self._format())
+
+

@@ -8,7 +8,8 @@ whole device batches of decoder records (one meta per image) without leaving the
 
 The forward direction, eval_coco.preprocess_factory's chain from images to normalised input
 tensors and metas, is `EvalPreprocess` (preprocess.py), and with the reference's extended
-scale, turns and multi-scale input pyramid `EvalViews` (preprocess_views.py).
+scale, turns and multi-scale input pyramid `EvalViews` (preprocess_views.py); both are one
+planner and batch engine (preprocess.py) over one C source (csrc/preprocess.hip).
 """
 import copy
 import ctypes

@@ -298,14 +298,34 @@ BAD_ARGS = [
     ('NULL mean', dict(mean=False), PP_EINVAL, 'NULL'),
     ('NULL fill', dict(fill=False), PP_EINVAL, 'NULL'),
 ]
+# pp_last_error() of every row as the library gave it before both entries shared one host
+# layer, after the entry's name and ': ' (recorded from that build, not from this one)
+_EDGE = 'a source or target edge < 2'
+_FIT = 'the target does not fit its output with this pad'
+_REGION = 'an output region beyond the output buffer'
+_STD = 'std must be finite and not 0'
+BAD_ARGS_TEXT = {
+    'h=1': _EDGE, 'w=1': _EDGE, 'th=1': _EDGE, 'tw=0': _EDGE,
+    'left too large': _FIT, 'top too large': _FIT, 'left<0': _FIT, 'H too small': _FIT,
+    'H=0': 'output size out of range', 'W=-3': 'output size out of range',
+    'out region beyond buffer': _REGION, 'out buffer short': _REGION,
+    'src beyond buffer': 'a source image beyond the source buffer',
+    'n_img=-1': 'n_img < 0',
+    'dtype=4': 'unknown dtype', 'dtype=-1': 'unknown dtype', 'layout=2': 'unknown layout',
+    'std 0': _STD, 'std inf': _STD, 'std nan': _STD,
+    'NULL src': 'NULL argument', 'NULL descs': 'NULL argument', 'NULL out': 'NULL argument',
+    'NULL mean': 'NULL argument', 'NULL fill': 'NULL argument',
+}
 
 
 @pytest.mark.parametrize('device', [False, True], ids=['cpu', 'device'])
 @pytest.mark.parametrize('case', BAD_ARGS, ids=[c[0] for c in BAD_ARGS])
 def test_bad_arguments(lib, case, device):
-    _, kwargs, code, word = case
+    name, kwargs, code, word = case
     assert _call(lib, device, **kwargs) == code
     assert word in lib.pp_last_error().decode()
+    entry = 'pp_preprocess_images' if device else 'pp_preprocess_images_cpu'
+    assert lib.pp_last_error().decode() == '{}: {}'.format(entry, BAD_ARGS_TEXT[name])
 
 
 def test_null_tables_and_empty_batch(lib):

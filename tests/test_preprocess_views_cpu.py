@@ -403,14 +403,38 @@ BAD_ARGS = [
     ('src beyond buffer', dict(src_offset=1), PP_ESHAPE, 'beyond the source buffer'),
     ('n_img=-1', dict(n=-1), PP_ESHAPE, 'n_img'),
 ]
+# pp_last_error() of every row as the library gave it before both entries shared one host
+# layer, after the entry's name and ': ' (recorded from that build, not from this one)
+_SQUARE = 'reduced or mirrored views need a square output (H == W)'
+_REGION = 'a view region beyond the output buffer'
+_MASK = 'empty or unknown reduction mask'
+BAD_ARGS_TEXT = {
+    'turn of a non-square': 'a turn needs a square output (H == W)',
+    'pyramid of a non-square': _SQUARE, 'mirror of a non-square': _SQUARE,
+    'two views of a non-square': _SQUARE,
+    'last view beyond buffer': _REGION, 'view offset beyond buffer': _REGION,
+    'negative view offset': _REGION,
+    'empty mask': _MASK, 'unknown mask': _MASK, 'negative mask': _MASK,
+    'rot=4': 'rot must be 0, 1, 2 or 3', 'rot=-1': 'rot must be 0, 1, 2 or 3',
+    'dtype=4': 'unknown dtype', 'layout=2': 'unknown layout',
+    'NULL src': 'NULL argument', 'NULL images': 'NULL argument', 'NULL offsets': 'NULL argument',
+    'NULL out': 'NULL argument', 'NULL mean': 'NULL argument', 'NULL fill': 'NULL argument',
+    'std 0': 'std must be finite and not 0',
+    'h=1': 'a source or target edge < 2',
+    'left too large': 'the target does not fit its output with this pad',
+    'src beyond buffer': 'a source image beyond the source buffer',
+    'n_img=-1': 'n_img < 0',
+}
 
 
 @pytest.mark.parametrize('device', [False, True], ids=['cpu', 'device'])
 @pytest.mark.parametrize('case', BAD_ARGS, ids=[c[0] for c in BAD_ARGS])
 def test_bad_arguments(lib, case, device):
-    _, kwargs, code, word = case
+    name, kwargs, code, word = case
     assert _call(lib, device, **kwargs) == code
     assert word in lib.pp_last_error().decode()
+    entry = 'pp_preprocess_views' if device else 'pp_preprocess_views_cpu'
+    assert lib.pp_last_error().decode() == '{}: {}'.format(entry, BAD_ARGS_TEXT[name])
 
 
 def test_tables_and_empty_batch(lib):

@@ -104,10 +104,11 @@ def main():
         g = g.view(torch.int16).numpy().astype(np.uint16) if dtype == torch.bfloat16 else g.numpy()
         assert np.array_equal(g.view(want.dtype), np.ascontiguousarray(want)), 'device != host twin'
 
-        _, plans, descs, src_bytes, out_elems, _ = pp._plan(dev_images, None)
+        _, _, rows, offsets, src_bytes, out_elems, _ = pp._plan(dev_images, None)
+        descs = preprocess.image_descs(rows, offsets)
         out_bytes = out_elems * torch.empty(0, dtype=dtype).element_size()
         pp.batch(dev_images)  # gathers the source buffer and sizes the kept output
-        routes = {'launch': lambda: pp._launch(descs, src_bytes, pp._out, out_elems),
+        routes = {'launch': lambda: pp._launch_descs(descs, src_bytes, pp._out, out_elems),
                   'device': lambda: pp.batch(dev_images),
                   'host': lambda: pp.batch(host_images)}
         for _ in range(args.warmup):

@@ -1,17 +1,19 @@
-// preprocess_views_asan_main.hip — sanitizer driver for pp_preprocess_views_cpu, the host twin
-// of the eval preprocessing kernel with turns and the input pyramid
-// (csrc/preprocess_views.hip with csrc/preprocess_pixel.hpp; the kernel runs the same
+// preprocess_asan_main.hip — sanitizer driver for pp_preprocess_views_cpu and
+// pp_preprocess_images_cpu, the host twin of the eval preprocessing kernels
+// (csrc/preprocess.hip with csrc/preprocess_pixel.hpp; the kernels run the same
 // __host__ __device__ index arithmetic).  Host code only, a program of its own; build and
 // run where no GPU is needed:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host \
 //       -fsanitize=address,undefined -I include -I openpifpaf_amd/csrc \
-//       openpifpaf_amd/csrc/preprocess_views.hip tools/preprocess_views_asan_main.hip \
-//       -o views_asan && ./views_asan
+//       openpifpaf_amd/csrc/preprocess.hip tools/preprocess_asan_main.hip \
+//       -o preprocess_asan && ./preprocess_asan
 //
-// Three random images per call at every canvas edge from 2 to 70, random turns, reduction
-// masks, mirror on and off, four dtypes and both layouts, with the source and the output
-// allocated to their exact sizes, so an access past an end aborts.  Prints "views asan ok".
+// Views: three random images per call at every canvas edge from 2 to 70, random turns,
+// reduction masks, mirror on and off, four dtypes and both layouts.  Images: three per call
+// on H x W canvases with H != W, both from 2 to 70.  The source and the output are allocated
+// to their exact sizes, so an access past an end aborts.  Prints "views asan ok" and
+// "images asan ok".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -73,5 +75,34 @@ int main() {
                         runs++;
                     }
     printf("views asan ok: %d runs\n", runs);
+    runs = 0;
+    for (int H = 2; H <= 70; H++)
+        for (int W = 2 + H % 3; W <= 70; W += 3)
+            for (int dtype = 0; dtype < 4; dtype++)
+                for (int layout = 0; layout < 2; layout++) {
+                    if (H == W) continue;
+                    const int n_img = 3;
+                    std::vector<pp_image_desc> im(n_img);
+                    int64_t so = 0, oo = 0;
+                    for (int i = 0; i < n_img; i++) {
+                        pp_image_desc &d = im[i];
+                        d.h = 2 + nxt() % 20; d.w = 2 + nxt() % 20;
+                        d.th = 2 + nxt() % (H - 1); d.tw = 2 + nxt() % (W - 1);
+                        d.left = (W - d.tw) / 2; d.top = (H - d.th) / 2; d.H = H; d.W = W;
+                        d.src_offset = so; d.out_offset = oo;
+                        so += (int64_t)d.h * d.w * 3;
+                        oo += 3LL * H * W;
+                    }
+                    const size_t es = dtype == 0 ? 4 : dtype == 3 ? 1 : 2;
+                    uint8_t *src = (uint8_t *)malloc((size_t)so);
+                    for (int64_t k = 0; k < so; k++) src[k] = (uint8_t)nxt();
+                    void *out = malloc((size_t)oo * es);
+                    memset(out, 0xAB, (size_t)oo * es);
+                    const int rc = pp_preprocess_images_cpu(src, so, im.data(), n_img, out, oo, dtype, layout, mean, sd, fill);
+                    if (rc != 0) { printf("rc %d at H %d W %d\n", rc, H, W); return 1; }
+                    free(src); free(out);
+                    runs++;
+                }
+    printf("images asan ok: %d runs\n", runs);
     return 0;
 }
