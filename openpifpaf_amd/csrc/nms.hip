@@ -77,7 +77,9 @@ constexpr int kNmsNarrow = 4;
 static_assert(kNmsBoxLists >= kNmsWaves, "one box list per NMS wave");
 // boxes per plane kept in REGISTERS, kNmsRegBoxes per lane (box i: lane i % 64, slot
 // i / 64), global scratch beyond: a check is ALU over the lane's slots plus one wave sum,
-// and the kernel needs no LDS for them (it fits beside the seed loop's 104 KB).  With the
+// and the kernel needs no LDS for them: beside a seed-loop workgroup (124,608 B) and a set-A
+// workgroup (37,440 B) a CU has 1,792 B left, which nms_kernel<4, 0> stays inside
+// (tests/test_nms_resources.py).  With the
 // list in LDS (448 per plane) and global memory beyond, uniform cfg5 (1370 annotations per
 // image) spent 20M cycles per image in the suppression pass on global-list loads.
 constexpr int kNmsRegBoxes = 24;
@@ -207,8 +209,270 @@ __device__ __forceinline__ void nms_plane_boxes(const GrowArgs &g, pp_ann *work,
     }
 }
 
-// PHASE 0: the whole of nms.Keypoints.annotations in one launch (suppression planes by
-// nms_plane_boxes); 1: up to the sorted keep list, whose count and occupancy-grid shape go
+// ---- nms.Keypoints.annotations for an image of at most kNmsSmall annotations ----
+// The same result as the general path of nms_kernel<W, 0> below, bit for bit and byte for byte
+// in work[]; only the schedule differs.  With one lane per annotation nothing has to be walked
+// pose by pose or sorted through memory:
+// - scores: lane j holds joint j of the annotation, the rank of v_j comes from K readlanes of
+//   the lane-held v (ann_score_lanes) and the per-annotation maxima from an ordered readlane
+//   walk (the `a > ax ? a : ax` chain from joint 0 on, which has the reference's NaN behaviour);
+// - sorts: a kept score is never NaN (`sc >= it` is false for NaN), so "-score ascending, then
+//   index ascending" is a strict total order and any correct sort gives the stable sort's
+//   permutation: each lane counts the kept lanes that come before it, by sort_by_score's
+//   comparator (-0.0 and +0.0 tie), over readlanes of the double;
+// - planes: lane r holds joint f of the r-th sorted annotation, its cell and its box.  Bit q
+//   of lane r's row mask says that q < r and box q covers cell r; the plane is then resolved
+//   in order over two scalar masks (marked, suppressed).  At most 63 earlier boxes cover a
+//   cell, so the reference's u8 count cannot wrap: "count non-zero mod 256" is "any".
+// Scores cross the waves through s_sc[] and the sorted work indices through s_ix[] (LDS, 576
+// B), the maxima through amax[] in the workspace; keep[] / perm[] / surv[] / flag[] / score[] /
+// kscore[] / gbox of the workspace are not written: nothing reads them after a PHASE 0 launch.
+// Records that carry their own score inputs (g.nms_spec, the standalone scored entry point)
+// stay on the general path.
+constexpr int kNmsSmall = 64;
+
+__device__ __forceinline__ double rl_d(double v, int l) {
+    return __hiloint2double(rl_i(__double2hiint(v), l), rl_i(__double2loint(v), l));
+}
+
+// ann_score_w with the default weights over lane-held confidences: lane j < K holds v_j (the
+// value of lanes >= K is ignored); collective over one wave, uniform result
+__device__ __forceinline__ double ann_score_lanes(ScoreLDS &L, float vj, int K) {
+    const int lane = threadIdx.x & 63;
+    const double ws = (double)(3 * min(K, 3) + (K - min(K, 3)));
+    int rank = 0;
+    for (int i = 0; i < K; i++) {
+        const float vi = rl_f(vj, i);
+        rank += (vi > vj) || (vi == vj && i < lane);
+    }
+    if (lane < K) L.prod[rank] = ((rank < 3 ? 3.0 : 1.0) / ws) * (double)vj;
+    wave_sync();
+    double res = 0.0;
+    if (lane == 0) res = pw_sum(L.prod, K);
+    wave_sync();  // prod[] may be written again
+    return rl_d(res, 0);
+}
+
+// the rank of this lane's (key, lane) among the lanes of `km` under sort_by_score's order
+__device__ __forceinline__ int nms_rank_lanes(uint64_t km, double key) {
+    const int lane = threadIdx.x & 63;
+    int rank = 0;
+    for (uint64_t rest = km; rest; rest &= rest - 1) {
+        const int q = __ffsll((unsigned long long)rest) - 1;
+        const double kq = rl_d(key, q);
+        rank += kq != key ? kq < key : q < lane;
+    }
+    return rank;
+}
+
+// returns the number of survivors written to out[] (with out_idx); the caller writes counts
+// and status.  s_m, s_m2, s_mx, s_my: the kernel's shared words.
+template <int W>
+__device__ __forceinline__ int nms_small(const GrowArgs &g, ScoreLDS &L, int img, pp_ann *work,
+                                         pp_ann *out, int n, float *amax, int &s_m, int &s_m2,
+                                         float &s_mx, float &s_my) {
+    __shared__ double s_sc[kNmsSmall];   // scores: by work index, sorted rank, output rank
+    __shared__ uint8_t s_ix[kNmsSmall];  // work indices: by sorted rank, then by output rank
+    const int K = g.K, cap = g.ann_cap;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float red = (float)g.cfg.occupancy_reduction;
+    const float kt = g.cfg.nms_keypoint_threshold;
+    const double it = g.nms_it;
+    STAMP_DECL
+    // nms.py:20-22: zero joints below keypoint_threshold; the scores and maxima per annotation
+    for (int i = wave; i < n; i += W) {
+        float x = 0.0f, y = 0.0f, v = 0.0f;
+        if (lane < K) {
+            x = work[i].data[lane][0];
+            y = work[i].data[lane][1];
+            v = work[i].data[lane][2];
+        }
+        const bool low = lane < K && v < kt;
+        if (low) x = y = v = 0.0f;
+        const double sc = ann_score_lanes(L, v, K);
+        float ax = rl_f(x, 0), ay = rl_f(y, 0);
+        for (int j = 1; j < K; j++) {
+            const float bx = rl_f(x, j), by = rl_f(y, j);
+            ax = bx > ax ? bx : ax;
+            ay = by > ay ? by : ay;
+        }
+        if (low) {
+            work[i].data[lane][0] = 0.0f;
+            work[i].data[lane][1] = 0.0f;
+            work[i].data[lane][2] = 0.0f;
+        }
+        if (lane == 0) {
+            s_sc[i] = sc;
+            amax[i] = ax;
+            amax[cap + i] = ay;
+        }
+    }
+    __syncthreads();
+    STAMP(2);
+    // the keep list in work order with the occupancy shape (nms.py:27-31) and the sort
+    // (nms.py:33), lane i for annotation i
+    if (wave == 0) {
+        const double sc = lane < n ? s_sc[lane] : 0.0;
+        const bool k = lane < n && sc >= it;
+        float ax = 0.0f, ay = 0.0f;
+        if (k) {
+            ax = amax[lane];
+            ay = amax[cap + lane];
+        }
+        const uint64_t km = __ballot(k);
+        int m = 0;
+        float mx = 0.0f, my = 0.0f;
+        for (uint64_t rest = km; rest; rest &= rest - 1) {  // in order (NaN behaviour)
+            const int l = __ffsll((unsigned long long)rest) - 1;
+            const float lx = rl_f(ax, l), ly = rl_f(ay, l);
+            if (m == 0 || lx > mx) mx = lx;
+            if (m == 0 || ly > my) my = ly;
+            m++;
+        }
+        const int rank = nms_rank_lanes(km, -sc);
+        if (k) s_ix[rank] = (uint8_t)lane;
+        if (lane == 0) {
+            s_m = m;
+            s_mx = mx;
+            s_my = my;
+        }
+    }
+    __syncthreads();
+    STAMP(3);
+    const int m = s_m;
+    int n_out = 0;
+    if (m > 0) {
+        // Occupancy((K, int(max y + 1), int(max x + 1)), 2, min_scale=4)
+        const long oh = (long)((double)(long)(s_my + 1.0f) / g.cfg.occupancy_reduction);
+        const long ow = (long)((double)(long)(s_mx + 1.0f) / g.cfg.occupancy_reduction);
+        const OccGrid no = occ_grid(nullptr, K, (int)(oh > 0 ? oh : 0), (int)(ow > 0 ? ow : 0));
+        // nms.py:34-45: wave w takes planes w, w + W, ...; their joints of the sorted
+        // annotations in one round trip
+        constexpr int kPlanes = (kKP + W - 1) / W;
+        const int wi0 = lane < m ? s_ix[lane] : 0;
+        float px[kPlanes], py[kPlanes], pv[kPlanes], ps[kPlanes];
+#pragma unroll
+        for (int u = 0; u < kPlanes; u++) {
+            const int f = wave + u * W;
+            px[u] = py[u] = pv[u] = ps[u] = 0.0f;
+            if (f < K && lane < m) {
+                px[u] = work[wi0].data[f][0];
+                py[u] = work[wi0].data[f][1];
+                pv[u] = work[wi0].data[f][2];
+                ps[u] = work[wi0].joint_scales[f];
+            }
+        }
+        // every plane's cells and boxes first (independent: their latencies overlap), then
+        // the planes' loops.  A plane beyond K has no live lane and no box.
+        int pcx[kPlanes], pcy[kPlanes], pbx[kPlanes], pby[kPlanes];
+        int fixed = 0;  // the same for every plane below K: the grid is empty or it is not
+#pragma unroll
+        for (int u = 0; u < kPlanes; u++) {
+            const int f = min(wave + u * W, K - 1);
+            int box[4] = {0, 0, 0, 0};
+            pcx[u] = pcy[u] = 0;
+            fixed = occ_cell(no, f, px[u], py[u], red, pcx[u], pcy[u]);  // uniform
+            const bool hb = wave + u * W < K && lane < m && !(pv[u] == 0.0f) &&
+                            occ_box(g, no, f, px[u], py[u], ps[u], box);
+            // (x0 | x1 << 16, y0 | y1 << 16); zero: covers nothing (x1 >= 1 with a box)
+            pbx[u] = hb ? box[0] | (box[1] << 16) : 0;
+            pby[u] = hb ? box[2] | (box[3] << 16) : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < kPlanes; u++) {
+            const int f = wave + u * W;
+            if (f < K) {
+                const float v = pv[u];
+                const int xi = pcx[u], yi = pcy[u], bxp = pbx[u], byp = pby[u];
+                const bool live = lane < m && !(v == 0.0f);  // nms.py:37 skips v == 0
+                const uint64_t lm = __ballot(live), bm = __ballot(bxp != 0);
+                uint32_t row_lo = 0u, row_hi = 0u;
+                if (fixed < 0) {
+                    for (uint64_t rest = bm; rest; rest &= rest - 1) {  // all cells per box
+                        const int q = __ffsll((unsigned long long)rest) - 1;
+                        const int bx = rl_i(bxp, q), by = rl_i(byp, q);
+                        const bool c = q < lane && xi >= (bx & 0xFFFF) && xi < (bx >> 16) &&
+                                       yi >= (by & 0xFFFF) && yi < (by >> 16);
+                        if (q < 32)
+                            row_lo |= c ? 1u << q : 0u;
+                        else
+                            row_hi |= c ? 1u << (q - 32) : 0u;
+                    }
+                }
+                // a cell that no earlier box covers is free whatever gets marked: its box
+                // counts from the start (only later rows can hold its bit), the walk skips it
+                const uint64_t nz = fixed < 0 ? __ballot((row_lo | row_hi) != 0u) : ~0ull;
+                uint64_t marked = bm & lm & ~nz, supp = 0;
+                for (uint64_t rest = lm & nz; rest; rest &= rest - 1) {  // in sorted order, scalar
+                    const int r = __ffsll((unsigned long long)rest) - 1;
+                    const uint64_t bit = 1ull << r;
+                    const uint64_t row = (uint64_t)(uint32_t)rl_i((int)row_lo, r) |
+                                         (uint64_t)(uint32_t)rl_i((int)row_hi, r) << 32;
+                    const bool occupied = fixed < 0 ? (row & marked) != 0 : fixed == 1;
+                    if (occupied)
+                        supp |= bit;
+                    else
+                        marked |= bm & bit;
+                }
+                if ((supp >> lane) & 1ull) work[wi0].data[f][2] = v * g.cfg.nms_suppression;
+            }
+        }
+        __syncthreads();
+        STAMP(4);
+        // nms.py:51-53 in sorted order: zero low joints, the scores again
+        for (int r = wave; r < m; r += W) {
+            const int wi = s_ix[r];
+            float v = 0.0f;
+            if (lane < K) v = work[wi].data[lane][2];
+            const bool low = lane < K && v < kt;
+            if (low) v = 0.0f;
+            const double sc = ann_score_lanes(L, v, K);
+            if (low) {
+                work[wi].data[lane][0] = 0.0f;
+                work[wi].data[lane][1] = 0.0f;
+                work[wi].data[lane][2] = 0.0f;
+            }
+            if (lane == 0) s_sc[r] = sc;
+        }
+        __syncthreads();
+        STAMP(6);
+        // survivors in sorted order and the second sort (nms.py:53-54), lane r for rank r
+        if (wave == 0) {
+            const double sc = lane < m ? s_sc[lane] : 0.0;
+            const int wi = lane < m ? s_ix[lane] : 0;
+            const bool k = lane < m && sc >= it;
+            const uint64_t km = __ballot(k);
+            const int rank = nms_rank_lanes(km, -sc);
+            wave_sync();  // every lane has read its slots
+            if (k) {
+                s_sc[rank] = sc;
+                s_ix[rank] = (uint8_t)wi;
+            }
+            if (lane == 0) s_m2 = __popcll(km);
+        }
+        __syncthreads();
+        STAMP(7);
+        n_out = s_m2;
+        for (int r = wave; r < n_out; r += W) {
+            const int wi = s_ix[r];
+            copy_ann(&out[r], &work[wi]);
+            if (lane == 0) {
+                out[r].score = s_sc[r];
+                if (g.out_idx) g.out_idx[(int64_t)img * cap + r] = wi;
+            }
+        }
+    }
+    __syncthreads();
+    STAMP(8);
+    if (wave == 0) {
+        STAMP_FLUSH(3);
+    }
+    return n_out;
+}
+
+// PHASE 0: the whole of nms.Keypoints.annotations in one launch (images of at most kNmsSmall
+// annotations by nms_small, the others' suppression planes by nms_plane_boxes); 1: up to the
+// sorted keep list, whose count and occupancy-grid shape go
 // to the meta words (nms_planes_kernel runs the planes); 3: from the suppressed planes on.
 template <int W, int PHASE = 0>
 __global__ __launch_bounds__(64 * W) void nms_kernel(GrowArgs g) {
@@ -258,6 +522,18 @@ __global__ __launch_bounds__(64 * W) void nms_kernel(GrowArgs g) {
             g.status[img] = s_status;
         }
         return;
+    }
+
+    if constexpr (PHASE == 0) {
+        // uniform over the workgroup: every barrier below and in nms_small stays uniform
+        if (n_anns <= kNmsSmall && !g.nms_spec) {
+            const int n_small = nms_small<W>(g, L, img, work, out, n_anns, amax, s_m, s_m2, s_mx, s_my);
+            if (threadIdx.x == 0) {
+                g.counts[img] = n_small;
+                g.status[img] = s_status;
+            }
+            return;
+        }
     }
 
     int m = 0;
